@@ -3,8 +3,13 @@
 769x769 Cityscapes-shaped synthetic crops, per-GPU batch 2 labeled + 2 unlabeled
 (BASELINE.json configs[2]/[3]: drop-in for train_semi.py's hot loop), fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: launched by torch.distributed.run, one rank per GPU, RCCL over xGMI)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the legs that take runs of their own
+after the timed steps: per-phase times, the roofline leg, lr-0.01 and epoch-0 samples, the direct-convolution leg, the
+exposed communication (N > 1), the CPU baseline and the config-5 leg (801x801, bf16 student; own process).
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/*.npy (see dump_outputs()).
 
 A step = one full optimizer step: teacher eval fwd (pseudo labels), CutMix, student
 fwd+bwd on 4 images, teacher train-mode fwd, OHEM sup loss (+aux), entropy /
@@ -46,6 +51,11 @@ def parse():
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--no-direct-leg", action="store_true", help="skip ms_per_step_direct / conv_error_vs_f64 (N = 1 only)")
     ap.add_argument("--no-config5-leg", action="store_true", help="skip the short BASELINE configs[4] leg (801x801, bf16 student)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the diagnostic legs (per-phase times, roofline, lr 0.01, epoch 0, "
+                         "direct convolutions, exposed communication, CPU baseline, config 5); the --no-* switches above "
+                         "select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -171,6 +181,24 @@ def wino_vs_direct_error(dev):
         KN.CONV_ALGO.update(saved)
     return {"layer": "3x3 256->256 d=2 @97x97 (layer3 conv2)", "max_err_over_max_vs_f64": {k: float("%.3g" % v) for k, v in out.items()},
             "winograd_over_direct": round(out["winograd_f4"] / max(out["direct"], 1e-30), 2)}
+
+
+def dump_outputs(path, trainer, meters, sample=1 << 20):
+    """--dump-outputs: what the last timed train_step handed its caller -- the loss meters it returned and the training state
+    it updated in place (student and teacher weights, the student's SGD momentum) -- as float32 .npy files.  The flat arenas
+    hold ~60 M floats each: every one is sampled at the same `sample` positions, one seeded draw per stratum of n / sample
+    consecutive floats (12 MB in all).  Same arguments -> same inputs, so two builds can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    n = trainer.arena.flat.numel()
+    k = min(n, sample)
+    stride = n // k
+    idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, k)
+    idx_d = torch.from_numpy(idx).to(trainer.arena.flat.device)
+    arrays = {"losses": meters, "student_weights": trainer.arena.flat[idx_d], "teacher_weights": trainer.t_arena.flat[idx_d]}
+    if trainer.arena.momentum_buf is not None:
+        arrays["student_momentum"] = trainer.arena.momentum_buf[idx_d]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def main():
@@ -324,6 +352,8 @@ def main():
     value = imgs / (ms / 1e3)
     comm = {k: (KN.COMM_STATS.get(k, 0) - comm0.get(k, 0)) / args.steps for k in set(comm0) | set(KN.COMM_STATS)}
     route1 = HO.split_route_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, meters)
     from u2pl_amd import roofline as RL
 
     def timed_steps(n, first, fn=None):
@@ -346,8 +376,8 @@ def main():
             dist.all_reduce(tb, op=dist.ReduceOp.MAX)
         return float(tb) / n * 1e3
 
-    diag = {}
-    if multi:
+    diag, roof = {}, {}
+    if multi and args.full:
         # exposed communication of the bucketed gradient all-reduce: the same steps with every bucket launched AFTER backward
         os.environ["U2PL_NO_BUCKET_OVERLAP"] = "1"
         diag["ms_per_step_no_bucket_overlap"] = round(timed_steps(3, args.warmup + args.steps), 3)
@@ -357,47 +387,48 @@ def main():
     diag["per_rank_ms"] = per_rank_ms       # each rank's own K steps + queue drain, before the closing barrier (max = the headline's clock)
     if world == 1:
         diag["comm_exposed_ms"] = 0.0
-    # per-phase time (the reference's meters: train_semi.py:563-587): ONE extra step with the side streams folded
-    # into the main stream (teacher passes, weight gradients) and an event at every phase boundary.  Serialised, the phases
-    # add up to more than the overlapped step (`phase_sum_ms` vs `ms_per_step`): what the side streams hide is the difference.
-    KNp = KN
-    trainer.train_step(*batches[0], epoch=1)     # (warm: same allocator / operand state as the timed steps)
-    torch.cuda.synchronize()
-    saved_side, saved_wg = getattr(trainer, "_side", None), KNp._WGRAD["enabled"]
-    trainer._side, KNp._WGRAD["enabled"] = torch.cuda.current_stream(), False
-    try:
-        # (this configuration has its own graph key -- the weight-gradient fork is part of it -- so the step runs eagerly: one
-        #  un-timed step first, which lets the caching allocator grow to the eager step's working set outside the measurement)
-        trainer.train_step(*batches[0], epoch=1)
+    if args.full:
+        # per-phase time (the reference's meters: train_semi.py:563-587): ONE extra step with the side streams folded
+        # into the main stream (teacher passes, weight gradients) and an event at every phase boundary.  Serialised, the phases
+        # add up to more than the overlapped step (`phase_sum_ms` vs `ms_per_step`): what the side streams hide is the difference.
+        KNp = KN
+        trainer.train_step(*batches[0], epoch=1)     # (warm: same allocator / operand state as the timed steps)
         torch.cuda.synchronize()
-        trainer.phase_log = []
-        trainer.train_step(*batches[1 % len(batches)], epoch=1)
-        torch.cuda.synchronize()
-        log = trainer.phase_log
-    finally:
-        trainer.phase_log = None
-        trainer._side, KNp._WGRAD["enabled"] = saved_side, saved_wg
-    phase_ms = {b[0]: round(a[1].elapsed_time(b[1]), 3) for a, b in zip(log[:-1], log[1:])}
-    diag["phase_ms"] = dict(phase_ms, comm_exposed=diag.get("comm_exposed_ms"))
-    diag["phase_sum_ms"] = round(sum(phase_ms.values()), 3)
-    diag["phase_ms_note"] = ("one extra step serialised on ONE stream (teacher passes and weight gradients folded into the main stream), "
-                             "HIP events at the phase boundaries; teacher_eval = pseudo-label pass + CutMix, student_fwd includes the "
-                             "supervised loss heads, contrastive = unsupervised CE + bank + InfoNCE forward, bwd = whole backward incl. "
-                             "weight gradients [+ bucket all-reduce launches], opt_ema = all-reduce join + SGD + EMA + operand re-split")
-    _progress()
-    if multi:
-        dist.barrier()
+        saved_side, saved_wg = getattr(trainer, "_side", None), KNp._WGRAD["enabled"]
+        trainer._side, KNp._WGRAD["enabled"] = torch.cuda.current_stream(), False
+        try:
+            # (this configuration has its own graph key -- the weight-gradient fork is part of it -- so the step runs eagerly: one
+            #  un-timed step first, which lets the caching allocator grow to the eager step's working set outside the measurement)
+            trainer.train_step(*batches[0], epoch=1)
+            torch.cuda.synchronize()
+            trainer.phase_log = []
+            trainer.train_step(*batches[1 % len(batches)], epoch=1)
+            torch.cuda.synchronize()
+            log = trainer.phase_log
+        finally:
+            trainer.phase_log = None
+            trainer._side, KNp._WGRAD["enabled"] = saved_side, saved_wg
+        phase_ms = {b[0]: round(a[1].elapsed_time(b[1]), 3) for a, b in zip(log[:-1], log[1:])}
+        diag["phase_ms"] = dict(phase_ms, comm_exposed=diag.get("comm_exposed_ms"))
+        diag["phase_sum_ms"] = round(sum(phase_ms.values()), 3)
+        diag["phase_ms_note"] = ("one extra step serialised on ONE stream (teacher passes and weight gradients folded into the main stream), "
+                                 "HIP events at the phase boundaries; teacher_eval = pseudo-label pass + CutMix, student_fwd includes the "
+                                 "supervised loss heads, contrastive = unsupervised CE + bank + InfoNCE forward, bwd = whole backward incl. "
+                                 "weight gradients [+ bucket all-reduce launches], opt_ema = all-reduce join + SGD + EMA + operand re-split")
+        _progress()
+        if multi:
+            dist.barrier()
 
-    # the roofline leg runs ONE extra (un-timed) step with per-call HIP events; it contains the step's
-    # collectives, so every rank executes it
-    KN.AMAX_STATS.update(fused=0, standalone=0)
-    roof = RL.measure(trainer, batches[0], args, ms)
-    # split-fp16 operand maxima of that (eager) step: how many came out of their producers' own launches, how many needed a pass
-    roof["operand_maxima_per_step"] = dict(KN.AMAX_STATS, conv_h=bool(KN.CONV_H["on"]))
-    _progress()
-    if multi:
-        dist.barrier()
-    if not args.no_calibrate:
+        # the roofline leg runs ONE extra (un-timed) step with per-call HIP events; it contains the step's
+        # collectives, so every rank executes it
+        KN.AMAX_STATS.update(fused=0, standalone=0)
+        roof = RL.measure(trainer, batches[0], args, ms)
+        # split-fp16 operand maxima of that (eager) step: how many came out of their producers' own launches, how many needed a pass
+        roof["operand_maxima_per_step"] = dict(KN.AMAX_STATS, conv_h=bool(KN.CONV_H["on"]))
+        _progress()
+        if multi:
+            dist.barrier()
+    if args.full and not args.no_calibrate:
         # the timed steps ran at lr 1e-6 (see above).  FIVE steps at the configuration's lr 0.01, each from the re-instated
         # calibrated state (weights, momentum, teacher, BatchNorm buffers restored and the derived operands rebuilt, un-timed:
         # the step after an lr-0.01 step would see collapsed pseudo-labels), through the same graph replays as the timed steps:
@@ -441,7 +472,7 @@ def main():
         diag["ms_per_step_epoch0_aliasing"] = round(timed_steps(3, 1, step_e0), 3)
         restore()
     wt = KN.CONV_ALGO["wino"]
-    if wt in (2, 4) and not args.bf16 and world == 1 and not args.no_direct_leg:
+    if args.full and wt in (2, 4) and not args.bf16 and world == 1 and not args.no_direct_leg:
         # the accuracy / speed trade of the default algorithm, in the line itself: the SAME workload with
         # every 3x3 layer on the direct implicit-GEMM kernel (U2PL_CONV_WINO=0), and both algorithms' error against float64
         KN.CONV_ALGO["wino"] = 0
@@ -525,7 +556,7 @@ def main():
         out["train_steps_in_process"] = n_steps_total[0]
         out["graphs"] = dict(GR.STATS, enabled=GR.enabled(), warm=GR.WARM, priming_steps_before_warmup=priming,
                              segments="teacher eval pass, teacher train pass, student forward, student backward")
-        if not args.no_cpu_baseline and world == 1:   # CPU baseline: rank 0 at N=1 only (the checker's port, never the product)
+        if args.full and not args.no_cpu_baseline and world == 1:   # CPU baseline: rank 0 at N=1 only (the checker's port, never the product)
             from oracle import step_ref
             out["cpu_baseline"] = step_ref.timed_cpu_baseline(crop=args.crop, arch=args.arch, batch=args.batch)
             import glob
@@ -540,9 +571,9 @@ def main():
                     "images_per_s": round(rt["reference_images_per_s"], 5), "cores": rt["cores"], "file": "profiles/" + os.path.basename(ref_t),
                     "note": "the reference's own train_semi.train() through oracle/ref_shim.py, 1 warm-up + 2 timed steps, "
                             "same configuration; /root/reference does not exist on the GPU box"}
-        if world == 1 and not args.bf16 and not args.no_config5_leg and args.crop == 769:
-            # BASELINE configs[4] ("config 5": 801x801, reduced-precision student, fp32 EMA teacher) as a short leg of the default
-            # run, so that the driver's line carries it; own process, after the headline measurement
+        if args.full and world == 1 and not args.bf16 and not args.no_config5_leg and args.crop == 769:
+            # BASELINE configs[4] ("config 5": 801x801, reduced-precision student, fp32 EMA teacher) as a short leg of the --full
+            # run, so that its line carries it; own process, after the headline measurement
             import gc
             import subprocess
             try:
@@ -551,7 +582,7 @@ def main():
                 gc.collect()
                 torch.cuda.empty_cache()
                 r5 = subprocess.run([sys.executable, os.path.abspath(__file__), "--bf16", "--crop", "801", "--steps", "4", "--warmup", "3",
-                                     "--no-cpu-baseline", "--no-config5-leg"], capture_output=True, text=True, timeout=600)
+                                     "--full", "--no-cpu-baseline", "--no-config5-leg"], capture_output=True, text=True, timeout=600)
                 l5 = [ln for ln in r5.stdout.splitlines() if ln.startswith("{")]
                 if not l5:
                     raise RuntimeError("no JSON line; rc %s; stderr tail: %s" % (r5.returncode, r5.stderr[-600:]))

@@ -234,7 +234,7 @@ def test_bucket_overlap_first_step_equals_reduce_after_backward():
 
 
 def test_bench_two_ranks_runs_and_reports_weak_scaling_line():
-    """bench.py under torch.distributed.run with 2 ranks (gloo, shared GPU): no hang in the roofline leg,
+    """bench.py --full under torch.distributed.run with 2 ranks (gloo, shared GPU): no hang in the roofline leg,
     one JSON line from rank 0 with the contract's keys."""
     import json
     import subprocess
@@ -243,7 +243,7 @@ def test_bench_two_ranks_runs_and_reports_weak_scaling_line():
     env = dict(os.environ, U2PL_DIST_BACKEND="gloo")   # (bench.py itself drops the persistent split when ranks share a GPU)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--arch", "resnet50", "--crop", "193"]
+           "--arch", "resnet50", "--crop", "193", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

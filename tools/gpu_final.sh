@@ -5,7 +5,7 @@ mkdir -p $O
 timeout 420 python -m pytest tests -q -m gpu < /dev/null > $O/tests.log 2>&1; echo "tests rc=$?"
 tail -4 $O/tests.log
 timeout 100 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" < /dev/null 2>&1 | tail -2
-timeout 200 python bench.py --steps 8 --warmup 3 < /dev/null > $O/bench_plain.json 2> $O/bench_plain.err; echo "plain rc=$?"
+timeout 200 python bench.py --full --steps 8 --warmup 3 < /dev/null > $O/bench_plain.json 2> $O/bench_plain.err; echo "plain rc=$?"
 python - <<'P'
 import json,os
 d=json.loads(open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r2z/bench_plain.json").read().strip().splitlines()[-1])

@@ -19,7 +19,7 @@ cat $O/STAMP.json
 # 8
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
-  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-direct-leg --no-config5-leg < /dev/null > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-direct-leg --no-config5-leg < /dev/null > $O/bench_$c.json 2> $O/bench_$c.err
   echo "pmc $c rc=$?"
 done
 python tools/parse_pmc_traffic.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE $O/traffic.json 8 10 $HEAD
@@ -29,7 +29,7 @@ timeout 1100 python -m pytest tests -q -m gpu < /dev/null > $O/tests.log 2>&1; e
 tail -4 $O/tests.log | cut -c1-300
 cp gpurun_out/full_size_parity.json gpurun_out/miou_gate.json $O/ 2>/dev/null
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" < /dev/null > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 700 python bench.py --steps 10 --warmup 4 < /dev/null > $O/bench_plain.json 2> $O/bench_plain.err; echo "plain rc=$?"
+timeout 700 python bench.py --full --steps 10 --warmup 4 < /dev/null > $O/bench_plain.json 2> $O/bench_plain.err; echo "plain rc=$?"
 python - <<'P'
 import json,os
 d=json.loads(open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r5final/bench_plain.json").read().strip().splitlines()[-1])
@@ -41,7 +41,7 @@ P
 prof() {   # name, extra env...
   n=$1; shift
   rm -rf /tmp/prof_$n
-  env "$@" timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$n -- python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-direct-leg --no-config5-leg < /dev/null > $O/bench_${n}_under_rocprof.json 2> $O/bench_${n}.err
+  env "$@" timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$n -- python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-direct-leg --no-config5-leg < /dev/null > $O/bench_${n}_under_rocprof.json 2> $O/bench_${n}.err
   echo "prof $n rc=$?"
   f=$(find /tmp/prof_$n -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/bench_${n}_kernel_stats.csv
@@ -107,5 +107,5 @@ P
 # 9
 timeout 200 python tools/host_overhead.py < /dev/null 2>&1 | grep -v amdgpu.ids > $O/host_overhead.txt; head -4 $O/host_overhead.txt
 # 10
-timeout 300 python bench.py --bf16 --crop 801 --steps 6 --warmup 3 --no-cpu-baseline --no-config5-leg < /dev/null > $O/bench_bf16_801.json 2> $O/bench_bf16_801.err; echo "bf16 rc=$?"
+timeout 300 python bench.py --full --bf16 --crop 801 --steps 6 --warmup 3 --no-cpu-baseline --no-config5-leg < /dev/null > $O/bench_bf16_801.json 2> $O/bench_bf16_801.err; echo "bf16 rc=$?"
 ls -la $O | head -40

@@ -1,5 +1,5 @@
 """Turn the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs as MI355X_MICROARCH.md
-prescribes) of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline` into profiles/rNN_traffic.json
+prescribes) of `python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline` into profiles/rNN_traffic.json
 (usage: parse_pmc_traffic.py <fetch_dir> <write_dir> <out.json> 6 10 [commit]  -- 6 full steps (1 warm-up + 3 timed + the recorded
 roofline step + the lr-0.01 sanity step), 10 replay repetitions of the HBM-bound group).
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of a wide coalesced stream -> x2."""
