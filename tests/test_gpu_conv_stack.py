@@ -244,6 +244,42 @@ def test_split_fp32_products_on_adversarial_operands(kind, C, O, k, d, H, W, ari
         # an fp32 dot product of length K is good to ~sqrt(K) .. K roundings; both arithmetics measured 1 .. 30 here
         assert errs[1][n] <= 1.5 * errs[0][n] + 4.0, (kind, n, errs)
         assert errs[1][n] < 64.0, (kind, n, errs)
+    if arith == "fp16x2" and kind == "mixed_magnitudes":
+        # the 12-decade case of the default arithmetic, held to the documented element-wise bound (tests/split_bounds.py)
+        _fp16x2_twelve_decades_elementwise(C, O, k, d, H, W, pad, g)
+
+
+def _fp16x2_twelve_decades_elementwise(C, O, k, d, H, W, pad, g):
+    import split_bounds as SB
+    Kn = K()
+    x = torch.randn(2, C, H, W, generator=g)
+    w = torch.randn(O, C, k, k, generator=g) / (k * k * C) ** 0.5
+    gy = torch.randn(2, O, H, W, generator=g)
+    sc = 10.0 ** (torch.rand(C, generator=g) * 12 - 6)
+    x, w = x * sc.view(1, C, 1, 1), w / sc.view(1, C, 1, 1)
+    saved, saved_h = dict(Kn.CONV_ALGO), dict(Kn.CONV_H)
+    try:
+        Kn.CONV_ALGO.update(wino=0)
+        Kn.CONV_H["on"] = True
+        conv = Kn.Conv2d(C, O, k, padding=pad, dilation=d, bias=False).to(DEV)
+        with torch.no_grad():
+            conv.weight.copy_(w.to(DEV))
+        xg = x.to(DEV).contiguous(memory_format=CL).requires_grad_(True)
+        with SB.recorded_calls(Kn) as seen:
+            y = conv(xg)
+            y.backward(gy.to(DEV).contiguous(memory_format=CL))
+            torch.cuda.synchronize()
+        got = dict(y=y.detach(), dx=xg.grad, dw=conv.weight.grad)
+    finally:
+        Kn.CONV_ALGO.update(saved)
+        Kn.CONV_H.update(saved_h)
+    # the split-fp16 entry points ran (not the six-product or fp32 kernels)
+    assert seen.get("u2pl_conv2d_fwd_wsh_f32") and seen.get("u2pl_conv2d_dgrad_wsh_f32") and seen.get("u2pl_conv2d_wgrad_h_f32"), \
+        sorted(seen)
+    ref = SB.conv_refs(x, w, gy, 1, pad, d)
+    for n in ("y", "dx", "dw"):
+        e = SB.excess(got[n], *ref[n])
+        assert e <= 1.0, ("twelve decades, fp16x2", n, e)
 
 
 def test_split_fp16_twelve_decades_inside_one_tensor_meet_the_documented_absolute_bound():
@@ -269,6 +305,35 @@ def test_split_fp16_twelve_decades_inside_one_tensor_meet_the_documented_absolut
         bound = (2.0 ** -40 * (float(xa.max()) * F.conv2d(torch.ones_like(xa), wa) + float(wa.max()) * F.conv2d(xa, torch.ones_like(wa)))
                  + 2.0 ** -22 * F.conv2d(xa, wa))
         assert bool(((y.cpu().double() - ref).abs() <= bound).all())
+        # the data and weight gradients (u2pl_conv2d_dgrad_wsh_f32 / u2pl_conv2d_wgrad_h_f32) and a Winograd 3x3 layer
+        # (u2pl_gemm_batched_wsh_f32 / u2pl_wgrad_batched_h_f32) under the element-wise bound of tests/split_bounds.py
+        import split_bounds as SB
+        gy = torch.randn(N, O, H, W, generator=g)
+        xg = x.to(DEV).contiguous(memory_format=CL).requires_grad_(True)
+        with SB.recorded_calls(Kn) as seen:
+            conv(xg).backward(gy.to(DEV).contiguous(memory_format=CL))
+            torch.cuda.synchronize()
+        assert seen.get("u2pl_conv2d_dgrad_wsh_f32") and seen.get("u2pl_conv2d_wgrad_h_f32"), sorted(seen)
+        bnd = SB.conv_refs(x, w, gy)
+        assert SB.excess(xg.grad, *bnd["dx"]) <= 1.0
+        assert SB.excess(conv.weight.grad, *bnd["dw"]) <= 1.0
+        Kn.CONV_ALGO.update(wino=4, min_gain=0.0)
+        w3 = torch.randn(O, C, 3, 3, generator=g) / (9 * C) ** 0.5 / sc.view(1, C, 1, 1)
+        conv3 = Kn.Conv2d(C, O, 3, padding=1, bias=False).to(DEV)
+        with torch.no_grad():
+            conv3.weight.copy_(w3.to(DEV))
+        xg = x.to(DEV).contiguous(memory_format=CL).requires_grad_(True)
+        with SB.recorded_calls(Kn) as seen:
+            y3 = conv3(xg)
+            y3.backward(gy.to(DEV).contiguous(memory_format=CL))
+            torch.cuda.synchronize()
+        # the Winograd split-fp16 kernels ran: forward + transposed component products and the Winograd-domain weight gradient
+        assert len(seen.get("u2pl_gemm_batched_wsh_f32", ())) == 2 and seen.get("u2pl_wgrad_batched_h_f32"), sorted(seen)
+        from u2pl_amd._lib import query
+        nsplit = query("u2pl_wgrad_batched_splits", query("u2pl_wino_tiles", N, H, W, 1, 4), C, O, 36)
+        assert SB.excess(y3, *SB.wino_conv(x, w3, 1, 4)) <= 1.0
+        assert SB.excess(xg.grad, *SB.wino_conv(gy, w3.flip(2, 3).transpose(0, 1), 1, 4)) <= 1.0
+        assert SB.excess(conv3.weight.grad, *SB.wino_wgrad(x, gy, 1, 4, nsplit)) <= 1.0
     finally:
         Kn.CONV_ALGO.update(saved)
         Kn.CONV_H.update(saved_h)

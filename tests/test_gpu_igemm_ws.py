@@ -5,8 +5,14 @@ fused BatchNorm statistics, fused eval-mode BatchNorm, data gradient, Winograd c
 BITS (the conv.hip kernels themselves are checked against torch fp32 / float64 in test_gpu_conv_stack.py).  Plus the
 once-per-step operand cache: a cached split must be rebuilt when the arena optimizer or a torch in-place op changes the
 weight, and only then."""
+import os
+import sys
+
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_bounds as SB  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -426,6 +432,13 @@ def test_wsh_forward_dgrad_wgrad_stats_against_float64(Cin, Cout, k, stride, dil
         e3 = float((got[True][i].cpu().double() - ref[i]).abs().max() / sc)
         assert e3 <= 1.25 * e6 + 2e-7, (name, e3, e6)
         assert e3 < 3e-6, (name, e3)
+    # ... and element-wise: a pixel whose dx is wrong relative to ITSELF fails here even when the max-normalised error passes
+    bnd = SB.conv_refs(x, conv.weight, gy, stride, dil * (k // 2), dil)
+    if bias:
+        bnd["y"] = (bnd["y"][0], bnd["y"][1] + SB.EPS * ref[0].abs())
+    for i, name in enumerate(("y", "dx", "dw")):
+        e = SB.excess(got[True][i], ref[i], bnd[name][1])
+        assert e <= 1.0, (name, e)
     # the fused BatchNorm statistics describe THIS arithmetic's output: equal to the stand-alone statistics pass over it to fp32
     # rounding of the column sums (both are pivot-shifted sums of the same values, added in different orders)
     ys, _, _, sums = _run_h(Kn, True, conv, x, gy, pivot)
@@ -471,6 +484,7 @@ def test_wsh_same_bits_across_tile_plans(Cin, Cout, k, stride, dil, H, W, N, bia
 
 @pytest.mark.parametrize("Cin,Cout,dil,H,W,N", [(256, 256, 2, 33, 29, 2), (512, 512, 4, 21, 21, 1), (128, 128, 1, 37, 37, 1)])
 def test_wsh_winograd_layers_against_float64(Cin, Cout, dil, H, W, N, wsh_switch):
+    from u2pl_amd._lib import query
     Kn = wsh_switch
     Kn.CONV_ALGO.update(wino=4, min_gain=0.0)
     torch.manual_seed(Cin + Cout + dil)
@@ -484,6 +498,13 @@ def test_wsh_winograd_layers_against_float64(Cin, Cout, dil, H, W, N, wsh_switch
         e6 = float((got[False][i].cpu().double() - ref[i]).abs().max() / sc)
         e3 = float((got[True][i].cpu().double() - ref[i]).abs().max() / sc)
         assert e3 <= 1.25 * e6 + 2e-7, (name, e3, e6)        # (the Winograd transforms dominate both: ~1e-5)
+    # element-wise, through the transforms (tests/split_bounds.py: F(4x4) restated from csrc/wino.hip)
+    nsplit = query("u2pl_wgrad_batched_splits", query("u2pl_wino_tiles", N, H, W, dil, 4), Cin, Cout, 36)
+    bounds = (SB.wino_conv(x, conv.weight, dil, 4), SB.wino_conv(gy, conv.weight.detach().flip(2, 3).transpose(0, 1), dil, 4),
+              SB.wino_wgrad(x, gy, dil, 4, nsplit))
+    for i, name in enumerate(("y", "dx", "dw")):
+        e = SB.excess(got[True][i], bounds[i][0], bounds[i][1])
+        assert e <= 1.0, (name, e)
 
 
 def test_fused_operand_maxima_equal_the_tensors_maxima(wsh_switch):

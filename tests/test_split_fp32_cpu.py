@@ -2,6 +2,7 @@
 the three-piece bf16 split is EXACT, and the six retained piece products reproduce an fp32 dot product to fp32 accuracy.
 (The GPU kernels are held to the same statement against float64 convolutions in tests/test_gpu_conv_stack.py.)"""
 import numpy as np
+import pytest
 
 
 def bf16_rne(x):
@@ -150,3 +151,77 @@ def test_scale_exponent_edge_cases():
     assert np.float32(3.4e38) * np.float32(2.0) ** split2_exp(3.4e38) < 2.0 ** 15
     assert split2_exp(0.0) == 126 and split2_exp(1e-45) == 126 # zero / subnormal maxima: the largest normal scale
     assert split2_exp(np.float32(np.inf)) == 14 - 128          # Inf / NaN maxima: a normal scale, the pieces come out Inf / NaN
+
+
+# ---- the element-wise bound the GPU route tests hold the kernels to (tests/split_bounds.py), and proof that it has teeth ----
+def _bounds():
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import split_bounds
+    return split_bounds
+
+
+def test_winograd_restatement_reproduces_the_float64_convolution():
+    """B^T, G, A^T restated from csrc/wino.hip (F(2x2) and F(4x4)), tiled over the polyphase sub-images of a dilated layer with
+    maps that are not a multiple of the tile: forward, data gradient (rotated taps, swapped channels) and the Winograd-domain
+    weight gradient equal F.conv2d and its autograd in float64"""
+    import torch
+    import torch.nn.functional as F
+    SB = _bounds()
+    g = torch.Generator().manual_seed(5)
+    for mt in (2, 4):
+        for dil, H, W in ((1, 9, 7), (2, 11, 10), (5, 6, 13), (3, 2, 5)):
+            x = torch.randn(2, 5, H, W, dtype=torch.float64, generator=g)
+            w = torch.randn(4, 5, 3, 3, dtype=torch.float64, generator=g)
+            xx, ww = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+            ref = F.conv2d(xx, ww, padding=dil, dilation=dil)
+            gy = torch.randn(ref.shape, dtype=torch.float64, generator=g)
+            ref.backward(gy)
+            y = SB.wino_conv(x, w, dil, mt, with_bound=False)
+            dx = SB.wino_conv(gy, w.flip(2, 3).transpose(0, 1), dil, mt, with_bound=False)
+            dw = SB.wino_wgrad(x, gy, dil, mt, with_bound=False)
+            for got, r in ((y, ref.detach()), (dx, xx.grad), (dw, ww.grad)):
+                assert float((got - r).abs().max()) <= 1e-12 * float(r.abs().max()), (mt, dil, H, W)
+
+
+def test_emulated_split_fp16_gemm_meets_the_element_wise_bound():
+    """the three-product split-fp16 GEMM (per-tensor power-of-two scales, fp16 subnormals honoured, fp32 accumulation per 16-deep
+    block) against float64 on the four operand kinds of the GPU tests, reduction lengths of a 1x1 and a 3x3 layer"""
+    SB = _bounds()
+    for K in (256, 1152):
+        for i, kind in enumerate(SB.KINDS):
+            A, B = SB.operands(kind, 192, K, 48, seed=10 + i)
+            ref = A.astype(np.float64) @ B.astype(np.float64)
+            got = SB.emulate_gemm(A, B)
+            assert SB.excess(got, ref, SB.gemm_bound(A.astype(np.float64), B.astype(np.float64))) <= 1.0, (kind, K)
+
+
+MUTANTS = {
+    "fp16 subnormals flushed": dict(flush=True),
+    "scale exponent 8 too small": dict(e_shift=-8),
+    "scale from the other operand": dict(swap_scales=True),
+    "a1 b0 dropped": dict(drop=0),
+    "a0 b1 dropped": dict(drop=1),
+    "a0 b0 dropped": dict(drop=2),
+    "maximum below the true one": "low_amax",
+}
+
+
+@pytest.mark.parametrize("mutant", list(MUTANTS))
+def test_the_bound_rejects_every_mutant_of_the_arithmetic(mutant):
+    """each mutant breaks the bound on the six-decade gradient rows (the loss heads' regime: elements of every size down to 2^-20
+    of the maximum), so a kernel that commits any of these errors fails the GPU route tests; the maximum below the truth gives
+    non-finite outputs on every kind"""
+    SB = _bounds()
+    kinds = SB.KINDS if MUTANTS[mutant] == "low_amax" else ("six_decade_rows",)
+    for i, kind in enumerate(kinds):
+        A, B = SB.operands(kind, 192, 1152, 48, seed=20 + i)
+        ref = A.astype(np.float64) @ B.astype(np.float64)
+        bound = SB.gemm_bound(A.astype(np.float64), B.astype(np.float64))
+        assert SB.excess(SB.emulate_gemm(A, B), ref, bound) <= 1.0, kind           # the faithful emulation passes on the same data
+        kw = dict(a_amax=float(np.abs(A).max()) / 4) if MUTANTS[mutant] == "low_amax" else MUTANTS[mutant]
+        got = SB.emulate_gemm(A, B, **kw)
+        assert SB.excess(got, ref, bound) > 1.0, (mutant, kind)
+        if MUTANTS[mutant] == "low_amax":
+            assert not np.isfinite(got).all(), kind
