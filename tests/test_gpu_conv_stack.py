@@ -415,6 +415,7 @@ def test_batchnorm_train_fwd_bwd_vs_torch(C, H, relu, res, drop):
         ref.running_mean.copy_(torch.randn(C, generator=g) * 0.1)
     mine = Kn.BatchNorm2d(C).to(DEV)
     mine.load_state_dict(ref.state_dict())
+    pivot, rv0 = ref.running_mean.double().clone(), ref.running_var.double().clone()
     xr = x.clone().requires_grad_(True)
     rr = r.clone().requires_grad_(True) if res else None
     yr = ref(xr)
@@ -438,6 +439,31 @@ def test_batchnorm_train_fwd_bwd_vs_torch(C, H, relu, res, drop):
     _close(mine.bias.grad, ref.bias.grad, rtol=5e-4, atol=1e-4, what="dbeta")
     _close(mine.running_mean, ref.running_mean, what="running_mean")
     _close(mine.running_var, ref.running_var, what="running_var")
+    # ... and element-wise against float64 (tests/bn_bounds.py): the stand-alone statistics (M <= 64: the float64 few-row kernel)
+    import bn_bounds as BB
+    M = N * H * H
+    rows = lambda t: t.detach().double().cpu().permute(0, 2, 3, 1).reshape(M, C)     # noqa: E731
+    X = rows(x)
+    L = None if M <= BB.SMALL_M else BB.L_standalone(M, C)
+    mu, var = BB.stats_ref(X)
+    e_mu, e_var, e1 = BB.stats_bound(X, pivot, L)
+    iota, e_iota, hi = BB.invstd_interval(var, e_var, float(np.float32(mine.eps)))
+    G, B = ref.weight.detach().double(), ref.bias.detach().double()
+    DR = dm.double().repeat_interleave(H * H, 0) if drop else None
+    pre, b = BB.apply_ref_bound(X, mu, iota, e_mu, e_iota, hi, G, B, rows(r) if res else None)
+    y64, by = BB.finish_y(pre, b, relu, DR)
+    Y = rows(yd)
+    assert BB.excess(Y, y64, by) <= 1.0
+    assert not relu or BB.mask_mismatch(pre, b, Y, DR) == 0
+    rm64, brm, rv64, brv = BB.running_ref_bound(pivot, rv0, mu, var, M, mine.momentum, e1, e_var)
+    assert BB.excess(mine.running_mean, rm64, brm) <= 1.0 and BB.excess(mine.running_var, rv64, brv) <= 1.0
+    bw = BB.bwd_ref_bound(X, rows(gy), (Y > 0).double() if relu else 1.0, DR, mu, iota, e_mu, e_iota, hi, G,
+                          BB.L_colreduce_chain(M, C))
+    assert BB.excess(rows(xd.grad), *bw["dx"]) <= 1.0
+    if res:
+        assert BB.excess(rows(rd.grad), *bw["dres"]) <= 1.0
+    for got, (S, e) in ((mine.weight.grad, bw["S1"]), (mine.bias.grad, bw["S0"])):
+        assert BB.excess(got, S, e * (1 + BB.EPS) + BB.EPS * S.abs()) <= 1.0
     # eval mode
     ref.eval(), mine.eval()
     _close(mine(xd.detach()), ref(x), what="eval fwd")
