@@ -482,6 +482,19 @@ def test_batchnorm_on_channel_slice_and_single_pixel():
     _close(mine2(x1.to(DEV), relu=True), F.relu(ref2(x1)), what="1x1")
 
 
+def test_batchnorm_residual_gradient_without_input_gradient_is_an_error():
+    """dres is written by the launch that writes dx: asking for the residual's gradient alone must raise, not hand autograd an
+    unwritten buffer (the models never ask: a residual goes into a BatchNorm whose input is a convolution's output)"""
+    Kn = K()
+    from u2pl_amd._lib import HipError
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 64, 9, 9, generator=g).to(DEV).contiguous(memory_format=CL)
+    r = torch.randn(2, 64, 9, 9, generator=g).to(DEV).contiguous(memory_format=CL).requires_grad_(True)
+    y = Kn.BatchNorm2d(64).to(DEV)(x, res=r, relu=True)
+    with pytest.raises(HipError):
+        y.sum().backward()
+
+
 @pytest.mark.parametrize("H,W", [(33, 35), (65, 65), (385, 385)])
 def test_maxpool_ceil_vs_torch(H, W):
     Kn = K()

@@ -13,6 +13,7 @@ Sequential indices); ``run_seq`` fuses them into the BatchNorm apply kernel.
 """
 import math
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -511,124 +512,183 @@ def finished_sums(pre, C, out=None):
     return pre
 
 
+# ---- the stages of a BatchNorm ------------------------------------------------------------------------------------------
+# forward: local statistics -> (exchange) -> finalise -> apply; backward: sums -> parameter gradients -> (exchange) -> apply.
+# _BNFn (one layer) and the two packed Functions further down (independent layers sharing one exchange) are written on these
+# functions, and each function is the only place in this file that names its C entries.  x, gy are as_rows() tensors.
+def _bn_local_sums(x, ldx, mod, pre_sums, out=None, fuse_finish=False):
+    """pivot-shifted LOCAL sums of one BatchNorm, double [2C+1] (written into `out` when given): the producing conv's epilogue
+    statistics where there are any, else one pass over x.  Slot 2C -- the row count of the packed protocol -- is never written:
+    the count is _exchange_count(M) by construction.  fuse_finish: no exchange stands between these sums and _bn_finalize, so
+    raw float32 partials are handed on as they are and finished inside the finalisation's launch (same bits)"""
+    N, C, H, W = x.shape
+    if pre_sums is not None:
+        if fuse_finish and FUSE_BN_FINISH and pre_sums.dtype == torch.float32:
+            return pre_sums
+        return finished_sums(pre_sums, C, out)
+    if out is None:
+        out = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+    wsb = _ws(query("u2pl_colreduce_workspace_bytes", N * H * W, 1, C), x.device)
+    call("u2pl_bn_stats_f32", x, ldx, N * H * W, C, mod.running_mean, wsb, out)
+    return out
+
+
+def _exchange_count(M):
+    """rows behind each channel's sums after a SyncBatchNorm exchange.  2C doubles per layer travel, the row count does not:
+    equal per-rank shapes (drop_last loaders) make it M * world on every rank, and writing it into a slot of the buffer from the
+    host cost a torch setitem per layer (~100 us of host time, 21 ms per step: RCCL in a world of one, tools/host_overhead.py)"""
+    return float(M * _world())
+
+
+def _bn_finalize(sums, count, mod):
+    """sums -> float32 mean, invstd of the batch; updates the running statistics and bumps the host-side num_batches_tracked
+    (see BatchNorm2d).  float32 `sums` are a conv epilogue's raw partials (_bn_local_sums): finish + finalisation in ONE launch"""
+    C = mod.num_features
+    mean = torch.empty(C, dtype=torch.float32, device=sums.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=sums.device)
+    if sums.dtype == torch.float32:
+        call("u2pl_bn_finish_finalize_f32", sums, sums.shape[0], C, count, mod.running_mean, mod.eps, mod.momentum, mean, invstd,
+             mod.running_mean, mod.running_var, None)
+    else:
+        call("u2pl_bn_finalize_f32", sums, count, mod.running_mean, C, mod.eps, mod.momentum, mean, invstd, mod.running_mean,
+             mod.running_var)
+    mod._nbt += 1
+    return mean, invstd
+
+
+def _bn_apply(x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, plain=False):
+    """y = [drop *] [relu]((x - mean) * invstd * gamma + beta [+ res]) as a new activation.  With split-fp16 on, the launch
+    also leaves max |y| for the convolutions that read y; plain: not wanted (y is read by another apply only)"""
+    N, C, H, W = x.shape
+    y = new_act(N, C, H, W, x.device)
+    if CONV_H["on"] and not plain:
+        y_amax = amax_slot(x.device)
+        call("u2pl_bn_apply_amax_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, int(relu), drop, H * W, y, C, N * H * W, C, y_amax)
+        set_amax(y, y_amax)
+    else:
+        call("u2pl_bn_apply_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, int(relu), drop, H * W, y, C, N * H * W, C)
+    return y
+
+
+def _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, out, gamma=None, rbeta=None):
+    """LOCAL backward sums of one BatchNorm into out (double [2C]: dbeta, then dgamma).  The ReLU mask is [y > 0] (y None: no
+    ReLU) or -- rbeta, the layer's beta, given -- recomputed from x with the forward's own expression"""
+    N, C, H, W = x.shape
+    wsb = _ws(query("u2pl_colreduce_workspace_bytes", N * H * W, 1, C), gy.device)
+    if rbeta is not None:
+        call("u2pl_bn_bwd_sums_mx_f32", gy, ldg, x, ldx, mean, invstd, gamma, rbeta, drop, H * W, N * H * W, C, wsb, out)
+    else:
+        call("u2pl_bn_bwd_sums_f32", gy, ldg, x, ldx, y, C, mean, invstd, drop, H * W, N * H * W, C, wsb, out)
+
+
+def _param_grads(sums, C, gsink, bsink, need):
+    """LOCAL parameter gradients from the (un-reduced) backward sums, like torch SyncBN (DDP averages them later):
+    dbeta = sums[:C], dgamma = sums[C:]; added into the arena sinks where the parameters have them, else returned"""
+    if not need:
+        return None, None
+    acc = gsink is not None
+    dgamma = gsink if acc else torch.empty(C, dtype=torch.float32, device=sums.device)
+    dbeta = bsink if acc else torch.empty(C, dtype=torch.float32, device=sums.device)
+    call("u2pl_sums_to_f32", sums[C:], C, 1.0, int(acc), dgamma)
+    call("u2pl_sums_to_f32", sums, C, 1.0, int(acc), dbeta)
+    if not acc:
+        return dgamma, dbeta
+    _mark_ready(gsink)
+    _mark_ready(bsink)
+    return None, None
+
+
+def _bn_bwd_apply(gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums, count, with_dres=False, pg=None, rbeta=None, maxima=False):
+    """-> dx, dres (the residual's gradient, when asked for) of one BatchNorm from the -- exchanged -- backward sums (None: eval
+    mode).  The three entries launch one kernel, k_bn_bwd_apply.  pg = (psums, gsink, bsink): the launch also adds the
+    parameter gradients, taken from the LOCAL sums psums, into the arena sinks.  rbeta: the ReLU mask from x (_bn_bwd_sums).
+    maxima: leave max |dx| / max |dres| for the data / weight gradients that read them (split-fp16)"""
+    N, C, H, W = x.shape
+    hw, M, dev = H * W, N * H * W, gy.device
+    dx = new_act(N, C, H, W, dev)
+    dres = new_act(N, C, H, W, dev) if with_dres else None
+    psums, gsink, bsink = pg or (None, None, None)
+    # the _amax entry is the only one with the maxima and the rbeta operands; it carries the parameter gradients too when asked
+    amax_entry = maxima or rbeta is not None
+    if amax_entry:
+        dx_amax = amax_slot(dev) if maxima else None
+        dres_amax = amax_slot(dev) if (with_dres and maxima) else None
+        call("u2pl_bn_bwd_apply_amax_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, hw, sums, count, dx, C, dres, C, M, C,
+             psums, gsink, bsink, 1, dx_amax, dres_amax, rbeta)
+        if dx_amax is not None:
+            set_amax(dx, dx_amax)
+        if dres_amax is not None:
+            set_amax(dres, dres_amax)
+    elif pg is not None:
+        call("u2pl_bn_bwd_apply_pg_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, hw, sums, count, dx, C, dres, C, M, C,
+             psums, gsink, bsink, 1)
+    else:
+        call("u2pl_bn_bwd_apply_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, hw, sums, count, dx, C, dres, C, M, C)
+    if pg is not None:
+        _mark_ready(gsink)
+        _mark_ready(bsink)
+    return dx, dres
+
+
 class _BNFn(torch.autograd.Function):
+    """one BatchNorm (+residual, ReLU, Dropout2d scale): single GPU, per-layer SyncBatchNorm exchange, eval mode"""
+
     @staticmethod
     def forward(ctx, x, gamma, beta, res, drop, mod, relu, gsink, bsink, pre_sums=None, link=None):
         x, ldx = as_rows(x)
         N, C, H, W = x.shape
-        M = N * H * W
-        dev = x.device
         ctx.link = link if res is not None else None
-        rr = ldr = None
-        if res is not None:
-            rr, ldr = as_rows(res)
-        y = new_act(N, C, H, W, dev)
-        training = mod.training
-        sync = mod.sync and dist_active()
-        if training:
-            pivot = mod.running_mean
-            mean = torch.empty(C, dtype=torch.float32, device=dev)
-            invstd = torch.empty(C, dtype=torch.float32, device=dev)
-            count = float(M)
-            if pre_sums is not None and pre_sums.dtype == torch.float32 and not sync and FUSE_BN_FINISH:
-                # single rank: ordered finish of the conv epilogue's partials + finalisation in ONE launch (same bits)
-                call("u2pl_bn_finish_finalize_f32", pre_sums, pre_sums.shape[0], C, count, pivot, mod.eps, mod.momentum, mean,
-                     invstd, mod.running_mean, mod.running_var, None)
-            else:
-                if pre_sums is not None:     # statistics came out of the producing conv's epilogue
-                    sums = finished_sums(pre_sums, C)
-                else:
-                    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-                    wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), dev)
-                    call("u2pl_bn_stats_f32", x, ldx, M, C, pivot, wsb, sums)
-                if sync:
-                    # (2C doubles travel; the row count does not: equal per-rank shapes -- drop_last loaders -- make it
-                    #  M * world on every rank.  Writing it into a slot of the buffer from the host cost a torch setitem per layer:
-                    #  ~100 us of host time, 21 ms per step -- measured on RCCL in a world of one, tools/host_overhead.py)
-                    _all_reduce(sums[:2 * C], "syncbn_allreduce", group=mod.group)
-                    count = float(M * _world())
-                call("u2pl_bn_finalize_f32", sums, count, pivot, C, mod.eps, mod.momentum, mean, invstd, mod.running_mean,
-                     mod.running_var)
-            mod._nbt += 1   # host counter; the buffer is materialised lazily (see BatchNorm2d)
+        rr, ldr = (None, 0) if res is None else as_rows(res)
+        exchange = mod.training and mod.sync and dist_active()
+        count = float(N * H * W)
+        if mod.training:
+            sums = _bn_local_sums(x, ldx, mod, pre_sums, fuse_finish=not exchange)
+            if exchange:
+                _all_reduce(sums[:2 * C], "syncbn_allreduce", group=mod.group)
+                count = _exchange_count(N * H * W)
+            mean, invstd = _bn_finalize(sums, count, mod)
         else:
-            mean = mod.running_mean
-            invstd = _eval_invstd(mod, C, dev)
-            count = float(M)
-        if CONV_H["on"]:        # split-fp16: max |y| for the convolutions that read y
-            y_amax = amax_slot(dev)
-            call("u2pl_bn_apply_amax_f32", x, ldx, mean, invstd, gamma, beta, rr, ldr or 0, int(relu), drop, H * W, y, C, M, C, y_amax)
-            set_amax(y, y_amax)
-        else:
-            call("u2pl_bn_apply_f32", x, ldx, mean, invstd, gamma, beta, rr, ldr or 0, int(relu), drop, H * W, y, C, M, C)
+            mean, invstd = mod.running_mean, _eval_invstd(mod, C, x.device)
+        y = _bn_apply(x, ldx, mean, invstd, gamma, beta, rr, ldr, relu, drop)
         # backward's ReLU mask: [y > 0] read from y, or -- no residual -- recomputed from x with the forward's own expression (same
         # bits; y is then neither saved nor read: 4 of 12-16 bytes per element in each of the two backward passes)
         ctx.mask_from_x = bool(relu and res is None and RELU_MASK_FROM_X and beta is not None)
         ctx.save_for_backward(x, y if (relu and not ctx.mask_from_x) else None, mean, invstd, gamma, drop,
                               beta if ctx.mask_from_x else None)
-        ctx.meta = (N, C, H, W, ldx, training, sync, count, res is not None)
+        ctx.meta = (ldx, mod.training, exchange, count, res is not None)
         ctx.gsink, ctx.bsink, ctx.group = gsink, bsink, mod.group
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, y, mean, invstd, gamma, drop, rbeta = ctx.saved_tensors
-        N, C, H, W, ldx, training, sync, count, has_res = ctx.meta
-        M = N * H * W
+        ldx, training, exchange, count, has_res = ctx.meta
+        need_dx, need_pg, need_dres = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_res and ctx.needs_input_grad[3]
+        if need_dres and not need_dx:
+            # (dres is written by the launch that writes dx.  The models do not get here: a residual only goes into a BatchNorm
+            #  whose input is a convolution's output, and that needs a gradient whenever the residual does)
+            raise HipError("BatchNorm backward: a residual gradient without an input gradient has no kernel form")
+        C = x.shape[1]
         gy, ldg = as_rows(gy)
-        dev = gy.device
-        sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), dev)
-        if rbeta is not None:
-            call("u2pl_bn_bwd_sums_mx_f32", gy, ldg, x, ldx, mean, invstd, gamma, rbeta, drop, H * W, M, C, wsb, sums)
+        sums = torch.empty(2 * C, dtype=torch.float64, device=gy.device)
+        _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, sums, gamma, rbeta)
+        maxima = CONV_H["on"]                            # split-fp16: the convolutions that read dx / dres want their maxima
+        amax_entry = maxima or rbeta is not None         # what _bn_bwd_apply then launches
+        # gradients into the arena: the two parameter-gradient writes ride in the apply launch (same arithmetic).  They are the
+        # LOCAL sums, the apply needs the exchanged ones: under an exchange only the _amax entry takes the two apart (psums)
+        pg_fused = FUSE_BN_FINISH and need_pg and ctx.gsink is not None and need_dx and (not exchange or amax_entry)
+        dgamma = dbeta = pg = None
+        if pg_fused:
+            # (one device copy of the local sums instead of two parameter-gradient launches in front of the exchange)
+            pg = (sums.clone() if exchange else sums, ctx.gsink, ctx.bsink)
         else:
-            call("u2pl_bn_bwd_sums_f32", gy, ldg, x, ldx, y, C, mean, invstd, drop, H * W, M, C, wsb, sums)
-        dgamma = dbeta = None
-        # single rank, gradients into the arena: the two parameter-gradient writes ride in the apply launch (same arithmetic)
-        pg_fused = (FUSE_BN_FINISH and ctx.needs_input_grad[1] and ctx.gsink is not None and ctx.needs_input_grad[0]
-                    and (not (sync and training) or CONV_H["on"] or rbeta is not None))
-        # (SyncBN: the parameter gradients are the LOCAL sums, the apply needs the all-reduced ones -- one device copy of the local
-        #  sums rides into the apply launch instead of two parameter-gradient launches in front of the exchange)
-        psums = sums
-        # parameter gradients are LOCAL sums (DDP averages them later), like torch SyncBN
-        if ctx.needs_input_grad[1] and not pg_fused:
-            if ctx.gsink is not None:
-                call("u2pl_sums_to_f32", sums[C:], C, 1.0, 1, ctx.gsink)
-                call("u2pl_sums_to_f32", sums, C, 1.0, 1, ctx.bsink)
-                _mark_ready(ctx.gsink)
-                _mark_ready(ctx.bsink)
-            else:
-                dgamma = torch.empty(C, dtype=torch.float32, device=dev)
-                dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-                call("u2pl_sums_to_f32", sums[C:], C, 1.0, 0, dgamma)
-                call("u2pl_sums_to_f32", sums, C, 1.0, 0, dbeta)
-        if sync and training:
-            if pg_fused:
-                psums = sums.clone()
+            dgamma, dbeta = _param_grads(sums, C, ctx.gsink, ctx.bsink, need_pg)
+        if exchange:
             _all_reduce(sums, "syncbn_allreduce", group=ctx.group)
-        dx = new_act(N, C, H, W, dev) if ctx.needs_input_grad[0] else None
-        dres = new_act(N, C, H, W, dev) if has_res and ctx.needs_input_grad[3] else None
-        if (CONV_H["on"] or rbeta is not None) and dx is not None:
-            # split-fp16: max |dx| / max |dres| for the data / weight gradients that read them; rbeta: the mask from x
-            dx_amax = amax_slot(dev) if CONV_H["on"] else None
-            dres_amax = amax_slot(dev) if (dres is not None and CONV_H["on"]) else None
-            call("u2pl_bn_bwd_apply_amax_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, H * W,
-                 sums if training else None, count, dx, C, dres, C, M, C, psums if pg_fused else None,
-                 ctx.gsink if pg_fused else None, ctx.bsink if pg_fused else None, 1, dx_amax, dres_amax, rbeta)
-            if dx_amax is not None:
-                set_amax(dx, dx_amax)
-            if dres_amax is not None:
-                set_amax(dres, dres_amax)
-            if pg_fused:
-                _mark_ready(ctx.gsink)
-                _mark_ready(ctx.bsink)
-        elif pg_fused:
-            call("u2pl_bn_bwd_apply_pg_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, H * W,
-                 sums if training else None, count, dx, C, dres, C, M, C, sums, ctx.gsink, ctx.bsink, 1)
-            _mark_ready(ctx.gsink)
-            _mark_ready(ctx.bsink)
-        elif dx is not None:
-            call("u2pl_bn_bwd_apply_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, H * W,
-                 sums if training else None, count, dx, C, dres, C, M, C)
+        dx = dres = None
+        if need_dx:
+            dx, dres = _bn_bwd_apply(gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums if training else None, count, need_dres,
+                                     pg, rbeta, maxima)
         if ctx.link is not None and dres is not None:
             dres = ctx.link.settle(dres)    # GradJoin: parked for the block's other consumer (conv1), or the total if it ran first
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
@@ -640,53 +700,10 @@ class _BNFn(torch.autograd.Function):
 # bottleneck of every ResNet stage, bn3 and the downsample BatchNorm (resnet.py:120-140).  Each group exchanges ONE packed
 # buffer forward and one backward instead of one all-reduce per layer.  Only used in train mode under a
 # process group with sync=True; everything else goes through _BNFn unit by unit (the single-GPU path is untouched).
-def _bn_apply(x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, hw, y, ldy, M, C):
-    """u2pl_bn_apply_f32; with split-fp16 on, the form that leaves max |y| for the convolutions that read y"""
-    if CONV_H["on"]:
-        y_amax = amax_slot(y.device)
-        call("u2pl_bn_apply_amax_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, hw, y, ldy, M, C, y_amax)
-        set_amax(y, y_amax)
-    else:
-        call("u2pl_bn_apply_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, hw, y, ldy, M, C)
-
-
-def _bn_local_sums(x, ldx, M, C, mod, pre_sums, out):
-    """pivot-shifted sums of one BatchNorm into out (double [2C+1], slot 2C = the local row count)"""
-    if pre_sums is not None:
-        finished_sums(pre_sums, C, out)
-    else:
-        wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), x.device)
-        call("u2pl_bn_stats_f32", x, ldx, M, C, mod.running_mean, wsb, out)
-    # (slot 2C -- the row count of the packed protocol -- stays what the caller's zero fill left: the count is M * world by
-    #  construction and a host-side setitem per unit costs ~100 us)
-
-
-def _bn_finalize(sums, count, mod, C, dev):
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-    call("u2pl_bn_finalize_f32", sums, count, mod.running_mean, C, mod.eps, mod.momentum, mean, invstd, mod.running_mean,
-         mod.running_var)
-    mod._nbt += 1
-    return mean, invstd
-
-
-def _param_grads(sums, C, gsink, bsink, need, dev):
-    """LOCAL parameter gradients from the (un-reduced) backward sums: dbeta = sums[:C], dgamma = sums[C:]"""
-    if not need:
-        return None, None
-    if gsink is not None:
-        call("u2pl_sums_to_f32", sums[C:], C, 1.0, 1, gsink)
-        call("u2pl_sums_to_f32", sums, C, 1.0, 1, bsink)
-        _mark_ready(gsink)
-        _mark_ready(bsink)
-        return None, None
-    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
-    dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-    call("u2pl_sums_to_f32", sums[C:], C, 1.0, 0, dgamma)
-    call("u2pl_sums_to_f32", sums, C, 1.0, 0, dbeta)
-    return dgamma, dbeta
-
-
+# What the packed Functions leave out of the single path's forms: their backward always reads the ReLU mask from the saved
+# y (never recomputed from x), writes the parameter gradients with u2pl_sums_to_f32 in front of the exchange (never inside
+# the apply) and takes the plain backward apply (no max |dx| under split-fp16: the gradient's consumers take their own).
+# The forward apply leaves max |y| as in _BNFn, except for the pair's downsample output, which only the second apply reads.
 class _BNGroupFn(torch.autograd.Function):
     """n independent train-mode SyncBatchNorms (+ReLU, Dropout2d scale) with ONE statistics all-reduce forward and ONE
     backward.  args: n, then per unit (x, gamma, beta, drop, pre_sums), then the per-unit python metadata list."""
@@ -694,33 +711,23 @@ class _BNGroupFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, *flat):
         meta = flat[5 * n]                      # [(mod, relu, gsink, bsink)] * n
-        units, total = [], 0
-        for i in range(n):
-            x, gamma, beta, drop, pre = flat[5 * i:5 * i + 5]
-            x, ldx = as_rows(x)
-            N, C, H, W = x.shape
-            units.append((x, ldx, N, C, H, W, gamma, beta, drop, pre))
-            total += 2 * C + 1
-        dev = units[0][0].device
+        units = [as_rows(flat[5 * i]) + flat[5 * i + 1:5 * i + 5] for i in range(n)]     # (x, ldx, gamma, beta, drop, pre_sums)
         group = meta[0][0].group
-        packed = torch.zeros(total, dtype=torch.float64, device=dev)
-        off = 0
-        for (x, ldx, N, C, H, W, gamma, beta, drop, pre), (mod, relu, gs, bs) in zip(units, meta):
-            _bn_local_sums(x, ldx, N * H * W, C, mod, pre, packed[off:off + 2 * C + 1])
-            off += 2 * C + 1
+        packed = torch.zeros(sum(2 * u[0].shape[1] + 1 for u in units), dtype=torch.float64, device=units[0][0].device)
+        slots, off = [], 0
+        for (x, ldx, gamma, beta, drop, pre), (mod, relu, gs, bs) in zip(units, meta):
+            slots.append(packed[off:off + 2 * x.shape[1] + 1])
+            off += 2 * x.shape[1] + 1
+            _bn_local_sums(x, ldx, mod, pre, slots[-1])
         _all_reduce(packed, "syncbn_allreduce", group=group)
-        outs, saved, ctx.meta, off = [], [], [], 0
-        W_ = _world()
-        for (x, ldx, N, C, H, W, gamma, beta, drop, pre), (mod, relu, gs, bs) in zip(units, meta):
-            M = N * H * W
-            count = float(M * W_)
-            mean, invstd = _bn_finalize(packed[off:off + 2 * C + 1], count, mod, C, dev)
-            off += 2 * C + 1
-            y = new_act(N, C, H, W, dev)
-            _bn_apply(x, ldx, mean, invstd, gamma, None if beta is None else beta, None, 0, int(relu), drop, H * W, y, C, M, C)
+        outs, saved, ctx.meta = [], [], []
+        for (x, ldx, gamma, beta, drop, pre), (mod, relu, gs, bs), sums in zip(units, meta, slots):
+            count = _exchange_count(x.numel() // x.shape[1])
+            mean, invstd = _bn_finalize(sums, count, mod)
+            y = _bn_apply(x, ldx, mean, invstd, gamma, beta, None, 0, relu, drop)
             outs.append(y)
             saved += [x, y if relu else None, mean, invstd, gamma, drop]
-            ctx.meta.append((N, C, H, W, ldx, count, gs, bs))
+            ctx.meta.append((ldx, count, gs, bs))
         ctx.save_for_backward(*saved)
         ctx.n, ctx.group = n, group
         return tuple(outs)
@@ -728,29 +735,22 @@ class _BNGroupFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gys):
         n, sv = ctx.n, ctx.saved_tensors
-        dev = gys[0].device
-        total = sum(2 * m[1] for m in ctx.meta)
-        packed = torch.empty(total, dtype=torch.float64, device=dev)
+        packed = torch.empty(sum(2 * sv[6 * i].shape[1] for i in range(n)), dtype=torch.float64, device=gys[0].device)
         work, off = [], 0
         for i in range(n):
             x, y, mean, invstd, gamma, drop = sv[6 * i:6 * i + 6]
-            N, C, H, W, ldx, count, gs, bs = ctx.meta[i]
-            M = N * H * W
+            ldx, count, gs, bs = ctx.meta[i]
+            C = x.shape[1]
             gy, ldg = as_rows(gys[i])
             sums = packed[off:off + 2 * C]
             off += 2 * C
-            wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), dev)
-            call("u2pl_bn_bwd_sums_f32", gy, ldg, x, ldx, y, C, mean, invstd, drop, H * W, M, C, wsb, sums)
-            dg, db = _param_grads(sums, C, gs, bs, ctx.needs_input_grad[1 + 5 * i + 1], dev)
-            work.append((gy, ldg, x, ldx, y, mean, invstd, gamma, drop, N, C, H, W, count, sums, dg, db))
+            _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, sums)
+            dg, db = _param_grads(sums, C, gs, bs, ctx.needs_input_grad[1 + 5 * i + 1])
+            work.append(((gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums, count), dg, db))
         _all_reduce(packed, "syncbn_allreduce", group=ctx.group)
         grads = [None]
-        for i, (gy, ldg, x, ldx, y, mean, invstd, gamma, drop, N, C, H, W, count, sums, dg, db) in enumerate(work):
-            dx = None
-            if ctx.needs_input_grad[1 + 5 * i]:
-                dx = new_act(N, C, H, W, dev)
-                call("u2pl_bn_bwd_apply_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, H * W, sums, count, dx, C, None, C,
-                     N * H * W, C)
+        for i, (args, dg, db) in enumerate(work):
+            dx = _bn_bwd_apply(*args)[0] if ctx.needs_input_grad[1 + 5 * i] else None
             grads += [dx, dg, db, None, None]
         grads.append(None)
         return tuple(grads)
@@ -767,44 +767,34 @@ class _BNResPairFn(torch.autograd.Function):
         xa, lda = as_rows(xa)
         xb, ldb = as_rows(xb)
         N, C, H, W = xa.shape
-        M, dev = N * H * W, xa.device
-        packed = torch.zeros(2 * (2 * C + 1), dtype=torch.float64, device=dev)
-        _bn_local_sums(xa, lda, M, C, mod_a, pre_a, packed[:2 * C + 1])
-        _bn_local_sums(xb, ldb, M, C, mod_b, pre_b, packed[2 * C + 1:])
+        packed = torch.zeros(2 * (2 * C + 1), dtype=torch.float64, device=xa.device)
+        _bn_local_sums(xa, lda, mod_a, pre_a, packed[:2 * C + 1])
+        _bn_local_sums(xb, ldb, mod_b, pre_b, packed[2 * C + 1:])
         _all_reduce(packed, "syncbn_allreduce", group=mod_a.group)
-        count = float(M * _world())
-        mean_a, inv_a = _bn_finalize(packed[:2 * C + 1], count, mod_a, C, dev)
-        mean_b, inv_b = _bn_finalize(packed[2 * C + 1:], count, mod_b, C, dev)
-        ident = new_act(N, C, H, W, dev)
-        call("u2pl_bn_apply_f32", xb, ldb, mean_b, inv_b, gb, bb, None, 0, 0, None, H * W, ident, C, M, C)
-        y = new_act(N, C, H, W, dev)
-        _bn_apply(xa, lda, mean_a, inv_a, ga, ba, ident, C, 1, None, H * W, y, C, M, C)
+        count = _exchange_count(N * H * W)
+        mean_a, inv_a = _bn_finalize(packed[:2 * C + 1], count, mod_a)
+        mean_b, inv_b = _bn_finalize(packed[2 * C + 1:], count, mod_b)
+        ident = _bn_apply(xb, ldb, mean_b, inv_b, gb, bb, None, 0, False, None, plain=True)
+        y = _bn_apply(xa, lda, mean_a, inv_a, ga, ba, ident, C, True, None)
         ctx.save_for_backward(xa, xb, y, mean_a, inv_a, mean_b, inv_b, ga, gb)
-        ctx.meta = (N, C, H, W, lda, ldb, count, gsa, bsa, gsb, bsb, mod_a.group)
+        ctx.meta = (lda, ldb, count, gsa, bsa, gsb, bsb, mod_a.group)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         xa, xb, y, mean_a, inv_a, mean_b, inv_b, ga, gb = ctx.saved_tensors
-        N, C, H, W, lda, ldb, count, gsa, bsa, gsb, bsb, group = ctx.meta
-        M, dev = N * H * W, gy.device
+        lda, ldb, count, gsa, bsa, gsb, bsb, group = ctx.meta
+        C = xa.shape[1]
         gy, ldg = as_rows(gy)
-        packed = torch.empty(4 * C, dtype=torch.float64, device=dev)
+        packed = torch.empty(4 * C, dtype=torch.float64, device=gy.device)
         sa, sb = packed[:2 * C], packed[2 * C:]
-        wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), dev)
-        call("u2pl_bn_bwd_sums_f32", gy, ldg, xa, lda, y, C, mean_a, inv_a, None, H * W, M, C, wsb, sa)
-        wsb2 = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, C), dev)
-        call("u2pl_bn_bwd_sums_f32", gy, ldg, xb, ldb, y, C, mean_b, inv_b, None, H * W, M, C, wsb2, sb)
-        dga, dba = _param_grads(sa, C, gsa, bsa, ctx.needs_input_grad[1], dev)
-        dgb, dbb = _param_grads(sb, C, gsb, bsb, ctx.needs_input_grad[5], dev)
+        _bn_bwd_sums(gy, ldg, xa, lda, y, mean_a, inv_a, None, sa)
+        _bn_bwd_sums(gy, ldg, xb, ldb, y, mean_b, inv_b, None, sb)
+        dga, dba = _param_grads(sa, C, gsa, bsa, ctx.needs_input_grad[1])
+        dgb, dbb = _param_grads(sb, C, gsb, bsb, ctx.needs_input_grad[5])
         _all_reduce(packed, "syncbn_allreduce", group=group)
-        dxa = dxb = None
-        if ctx.needs_input_grad[0]:
-            dxa = new_act(N, C, H, W, dev)
-            call("u2pl_bn_bwd_apply_f32", gy, ldg, xa, lda, y, C, mean_a, inv_a, ga, None, H * W, sa, count, dxa, C, None, C, M, C)
-        if ctx.needs_input_grad[4]:
-            dxb = new_act(N, C, H, W, dev)
-            call("u2pl_bn_bwd_apply_f32", gy, ldg, xb, ldb, y, C, mean_b, inv_b, gb, None, H * W, sb, count, dxb, C, None, C, M, C)
+        dxa = _bn_bwd_apply(gy, ldg, xa, lda, y, mean_a, inv_a, ga, None, sa, count)[0] if ctx.needs_input_grad[0] else None
+        dxb = _bn_bwd_apply(gy, ldg, xb, ldb, y, mean_b, inv_b, gb, None, sb, count)[0] if ctx.needs_input_grad[4] else None
         return dxa, dga, dba, None, dxb, dgb, dbb, None, None
 
 
@@ -888,7 +878,6 @@ RELU_MASK_FROM_X = os.environ.get("U2PL_NO_RELU_MASK_FROM_X") is None
 # model in one launch (eval_invstd)
 FUSE_BN_FINISH = os.environ.get("U2PL_NO_BN_FINISH_FUSION") is None
 _EVAL_INVSTD = {}
-import weakref  # noqa: E402
 _EVAL_PREP = weakref.WeakKeyDictionary()
 
 
@@ -1169,6 +1158,18 @@ class MaxPool3x3s2Ceil(nn.Module):
         return _MaxPoolFn.apply(x)
 
 
+def _image_colsums(x, ldx, scale):
+    """scale * (sum over each image's pixels) of as_rows() x -> float32 [N][C]"""
+    N, C, H, W = x.shape
+    sums = torch.empty((N, 2, C), dtype=torch.float64, device=x.device)
+    wsb = _ws(query("u2pl_colreduce_workspace_bytes", H * W, N, C), x.device)
+    call("u2pl_colsum_f32", x, ldx, H * W, N, C, wsb, sums)
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    for n in range(N):
+        call("u2pl_sums_to_f32", sums[n], C, scale, 0, out[n])
+    return out
+
+
 class _GapFn(torch.autograd.Function):
     """nn.AdaptiveAvgPool2d((1,1)) (base.py:24)."""
 
@@ -1176,12 +1177,7 @@ class _GapFn(torch.autograd.Function):
     def forward(ctx, x):
         x, ldx = as_rows(x)
         N, C, H, W = x.shape
-        sums = torch.empty((N, 2, C), dtype=torch.float64, device=x.device)
-        wsb = _ws(query("u2pl_colreduce_workspace_bytes", H * W, N, C), x.device)
-        call("u2pl_colsum_f32", x, ldx, H * W, N, C, wsb, sums)
-        y = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        for n in range(N):
-            call("u2pl_sums_to_f32", sums[n], C, 1.0 / (H * W), 0, y[n])
+        y = _image_colsums(x, ldx, 1.0 / (H * W))
         ctx.meta = (N, C, H, W)
         return y.reshape(N, C, 1, 1)
 
@@ -1214,13 +1210,7 @@ class _BroadcastFn(torch.autograd.Function):
     def backward(ctx, gy):
         N, C, H, W = ctx.meta
         gy, ldg = as_rows(gy)
-        sums = torch.empty((N, 2, C), dtype=torch.float64, device=gy.device)
-        wsb = _ws(query("u2pl_colreduce_workspace_bytes", H * W, N, C), gy.device)
-        call("u2pl_colsum_f32", gy, ldg, H * W, N, C, wsb, sums)
-        g = torch.empty((N, C), dtype=torch.float32, device=gy.device)
-        for n in range(N):
-            call("u2pl_sums_to_f32", sums[n], C, 1.0, 0, g[n])
-        return g.reshape(N, C, 1, 1), None, None
+        return _image_colsums(gy, ldg, 1.0).reshape(N, C, 1, 1), None, None
 
 
 class _UpsampleFn(torch.autograd.Function):
