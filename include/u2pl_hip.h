@@ -505,6 +505,33 @@ int u2pl_augment_u8_f32(const unsigned char* img, const unsigned char* lab, cons
                         int Sh, int Sw, const float* mean3, const float* std3, float* out_img, long long* out_lab,
                         hipStream_t stream);
 
+/* the same pipeline with the reference's two remaining transform options and batches of mixed image sizes
+   (augmentation.py:269-346 as composed by pascal_voc.py:48-71): ... RandResize -> RandRotate -> RandomGaussianBlur ->
+   flip -> crop.  One record of U2PL_AUG_REC int32 per sample (device):
+     [0] rh  [1] rw          size after RandResize (= H, W without it)
+     [2] flip                0 / 1
+     [3] pad_top [4] pad_left  zero padding of the crop (label 0 there)
+     [5] crop_y  [6] crop_x    crop origin in the padded frame
+     [7] flags               U2PL_AUG_ROTATE | U2PL_AUG_BLUR: what THIS sample gets (blur is a per-sample coin)
+     [8] H  [9] W            size of the decoded sample (read when offsets != NULL)
+     [10..13] m00 m01 m10 m11  bit patterns of the float32 rotation matrix handed to F.affine_grid
+                             ([[cos a, sin a], [-sin a, cos a]], translation 0); ignored without U2PL_AUG_ROTATE
+     [14] [15] 0
+   img / lab: uint8, sample b starts at pixel offsets[b] (img: 3 bytes per pixel, [H_b][W_b][3]; lab: [H_b][W_b]);
+   offsets == NULL: dense [B][H][W] layout, every sample H x W (the arguments; record words 8 and 9 are not read).
+   mode: U2PL_AUG_ROTATE / U2PL_AUG_BLUR set when the CONFIG enables the option (any sample of the batch may carry the
+   flag).  With U2PL_AUG_BLUR the call runs two passes through `scratch` (u2pl_augment_ex_scratch_bytes, fp32) and reads
+   blur_w, 25 float32 weights [ky][kx] on the device; otherwise both may be NULL.  Rotated-out pixels: image 0, label
+   ignore_label.  mean3 / std3 are HOST pointers.  Mode 0 on a dense batch gives the bits of u2pl_augment_u8_f32. */
+#define U2PL_AUG_REC 16
+#define U2PL_AUG_ROTATE 1
+#define U2PL_AUG_BLUR 2
+size_t u2pl_augment_ex_scratch_bytes(int B, int Sh, int Sw, int mode);
+int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned char* lab, const long long* offsets,
+                           const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
+                           const float* mean3, const float* std3, const float* blur_w, float* scratch, float* out_img,
+                           long long* out_lab, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

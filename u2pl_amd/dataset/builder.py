@@ -25,9 +25,39 @@ def parse_list(path):
     raise ValueError("unknown dataset list: " + path)
 
 
+DEAD_OPTIONS_MESSAGE = ("dataset option '{}' cannot work upstream either: its transform returns a 5- or 3-tuple that the "
+                        "reference's own __getitem__ cannot unpack (cityscapes.py:70-75); the strong augmentations of the "
+                        "unlabeled branch are trainer.unsupervised.apply_aug")
+
+
+def gaussian_blur_weights(radius=2):
+    """float32 (5,5) weights of the reference's GaussianBlur(radius) (augmentation.py:325-346), i.e. of
+    scipy.ndimage.gaussian_filter(delta, sigma=0.3*(radius-1)+0.8) restated in numpy: the 1-D kernel of radius
+    int(4*sigma+0.5), exp(-x^2/2sigma^2) normalised, correlated with the delta row under `reflect` extension;
+    the 2-D filter is separable, so the result is the outer product of that row with itself (float64, then cast)."""
+    n, sigma = 2 * radius + 1, 0.3 * (radius - 1) + 0.8
+    r = int(4.0 * sigma + 0.5)
+    x = np.arange(-r, r + 1)
+    k = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    k = k / k.sum()
+    delta = np.zeros(n)
+    delta[radius] = 1.0
+    ext = np.pad(delta, r, mode="symmetric")          # scipy's `reflect` (d c b a | a b c d | d c b a)
+    row = np.array([np.dot(ext[i:i + 2 * r + 1], k) for i in range(n)])
+    return np.outer(row, row).astype(np.float32)
+
+
+def rotation_matrix(angle):
+    """cv2.getRotationMatrix2D((0, 0), angle, 1) as float64 (2,3): OpenCV's formula, computed with `math`."""
+    a = angle * math.pi / 180.0
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, s, 0.0], [-s, c, 0.0]])
+
+
 class Pipeline:
-    """ToTensor -> Normalize -> [Resize] -> [RandResize] -> [Flip] -> [Crop] on (1,C,H,W) tensors;
-    python `random` draws in the reference's order (augmentation.py:51-266, cityscapes.py:47-77)."""
+    """ToTensor -> Normalize -> [Resize] -> [RandResize] -> [RandRotate] -> [RandomGaussianBlur] -> [Flip] -> [Crop]
+    on (1,C,H,W) tensors; python `random` draws in the reference's order (augmentation.py:51-346,
+    cityscapes.py:47-77, pascal_voc.py:48-71)."""
 
     def __init__(self, cfg):
         self.mean = torch.tensor(np.float32(cfg["mean"]))[None, :, None, None]
@@ -36,9 +66,13 @@ class Pipeline:
         self.rand_resize = cfg.get("rand_resize", False)
         self.flip = bool(cfg.get("flip", False))
         self.crop = cfg.get("crop", False)
-        for k in ("rand_rotation", "GaussianBlur", "cutout", "cutmix"):
+        self.rotation = cfg.get("rand_rotation", False)
+        self.ignore_label = cfg.get("ignore_label", 255)
+        self.blur = torch.from_numpy(gaussian_blur_weights())[None, None].repeat(3, 1, 1, 1) if cfg.get(
+            "GaussianBlur", False) else None
+        for k in ("cutout", "cutmix"):
             if cfg.get(k, False):
-                raise NotImplementedError(f"dataset option '{k}' is not enabled by any shipped config")
+                raise NotImplementedError(DEAD_OPTIONS_MESSAGE.format(k))
 
     def __call__(self, image, label):
         image = torch.from_numpy(np.asarray(image).copy().transpose(2, 0, 1)[None]).float()
@@ -54,6 +88,16 @@ class Pipeline:
             size = (int(h * s), int(w * s))
             image = F.interpolate(image, size=size, mode="bilinear", align_corners=False)
             label = F.interpolate(label, size=size, mode="nearest")
+        if self.rotation:   # RandRotate (augmentation.py:285-296): rotation about the origin of the NORMALISED grid
+            lo, hi = self.rotation
+            theta = torch.Tensor(rotation_matrix(lo + (hi - lo) * random.random())).unsqueeze(dim=0)
+            grid = F.affine_grid(theta, image.size(), align_corners=False)
+            image = F.grid_sample(image, grid, mode="bilinear", align_corners=False)
+            label = F.grid_sample(label + 1, grid, mode="nearest", align_corners=False)
+            label[label == 0.0] = self.ignore_label + 1     # what the zero padding of grid_sample left outside
+            label = label - 1
+        if self.blur is not None and random.random() < 0.5:   # RandomGaussianBlur (augmentation.py:315-346)
+            image = F.conv2d(image, self.blur, stride=1, padding=2, groups=3)
         if self.flip and random.random() < 0.5:
             image, label = torch.flip(image, [3]), torch.flip(label, [3])
         if self.crop:
@@ -100,8 +144,9 @@ def _loader(dset, cfg, train):
     ddp = torch.distributed.is_available() and torch.distributed.is_initialized()
     world, rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if ddp else (1, 0)
     sampler = DistributedSampler(dset, num_replicas=world, rank=rank, shuffle=train)
+    # (RawSegDataset brings its own collate: batches of mixed image sizes are packed, not stacked)
     return DataLoader(dset, batch_size=cfg.get("batch_size", 1), num_workers=cfg.get("workers", 2), sampler=sampler,
-                      shuffle=False, pin_memory=True, drop_last=train)
+                      shuffle=False, pin_memory=True, drop_last=train, collate_fn=getattr(dset, "collate_fn", None))
 
 
 def get_loader(cfg, seed=0):
@@ -116,21 +161,27 @@ def get_loader(cfg, seed=0):
 
     tc, vc = split_cfg("train"), split_cfg("val")
     val = SegDataset(vc["data_root"], vc["data_list"], Pipeline(vc), seed, None, "val")
+    plan = None
+    if d.get("device_aug", False):
+        # decoded uint8 samples + host-drawn geometry; the transform chain runs fused on the GPU (device_aug.py):
+        # engine.run finishes the batches with augment_batch.  Val loaders stay on the host chain.
+        from .device_aug import AugmentPlan, RawSegDataset
+        plan = AugmentPlan(tc)
+
+    def train_loader(dset):
+        if plan is None:
+            return _loader(dset, tc, True)
+        ld = _loader(RawSegDataset(dset, plan), tc, True)
+        ld.device_plan = plan
+        return ld
+
     if not semi:
         n_sup = tc.get("n_sup", TOTAL_TRAIN[kind]) if kind == "cityscapes" else None
         sup = SegDataset(tc["data_root"], tc["data_list"], Pipeline(tc), seed, n_sup, "train")
-        return _loader(sup, tc, True), _loader(val, vc, False)
+        return train_loader(sup), _loader(val, vc, False)
     # both sets are resampled to (total - n_sup) items (cityscapes.py:116-141, pascal_voc.py:109-134; Q12)
     n = TOTAL_TRAIN[kind] - tc.get("n_sup", TOTAL_TRAIN[kind])
     sup = SegDataset(tc["data_root"], tc["data_list"], Pipeline(tc), seed, n, "train")
     unsup = SegDataset(tc["data_root"], tc["data_list"].replace("labeled.txt", "unlabeled.txt"), Pipeline(tc), seed, n,
                        "train")
-    if d.get("device_aug", False):
-        # decoded uint8 samples + host-drawn geometry; the transform chain runs fused on the GPU (device_aug.py).
-        # Needs one image size per list (Cityscapes); engine.run finishes the batches with augment_batch.
-        from .device_aug import AugmentPlan, RawSegDataset
-        plan = AugmentPlan(tc)
-        ls, lu = _loader(RawSegDataset(sup, plan), tc, True), _loader(RawSegDataset(unsup, plan), tc, True)
-        ls.device_plan = lu.device_plan = plan
-        return ls, lu, _loader(val, vc, False)
-    return _loader(sup, tc, True), _loader(unsup, tc, True), _loader(val, vc, False)
+    return train_loader(sup), train_loader(unsup), _loader(val, vc, False)

@@ -201,15 +201,13 @@ def run(cfg, args, semi):
         for step, batch_l in enumerate(loader_l):
             if plan is not None:
                 from .dataset.device_aug import augment_batch
-                image_l, label_l = augment_batch(plan, batch_l[0].to(device, non_blocking=True),
-                                                 batch_l[1].to(device, non_blocking=True), batch_l[2])
+                image_l, label_l = augment_batch(plan, *batch_l, device=device)   # stacked (3) or packed (4 tensors)
             else:
                 image_l, label_l = batch_l[0].to(device, non_blocking=True), batch_l[1].to(device, non_blocking=True)
             if semi:
                 batch_u = next(it_u)
                 if plan is not None:
-                    image_u, _ = augment_batch(plan, batch_u[0].to(device, non_blocking=True),
-                                               batch_u[1].to(device, non_blocking=True), batch_u[2])
+                    image_u, _ = augment_batch(plan, *batch_u, device=device)
                 else:
                     image_u = batch_u[0].to(device, non_blocking=True)
                 meters = trainer.train_step(image_l, label_l, image_u, epoch)
