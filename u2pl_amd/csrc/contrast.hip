@@ -661,10 +661,11 @@ __global__ __launch_bounds__(64 * PR_WPB) void k_proto_stream(const float* __res
     P1_DBG_END(1, blockIdx.x)
 }
 
-// grid (C, D/64), 1024 threads: 64 channels x 16 row groups; the flagged blocks are first compacted (in
+// grid (C, D/64), 1024 threads: 64 channels x 16 row groups (pitchC: classes per block partial, the streaming kernel's
+// instantiation, >= gridDim.x); the flagged blocks are first compacted (in
 // ascending order) into an LDS list so that the partial loads are independent (8 in flight per thread)
 __global__ __launch_bounds__(1024) void k_proto_finish(const float* __restrict__ partial, int D,
-                                                       const unsigned* __restrict__ counts, int nblk, int C,
+                                                       const unsigned* __restrict__ counts, int nblk, int pitchC,
                                                        const unsigned* __restrict__ flags, float* __restrict__ proto) {
     __shared__ double sh[16][64];
     __shared__ int act[PF_MAXBLK];
@@ -695,11 +696,11 @@ __global__ __launch_bounds__(1024) void k_proto_finish(const float* __restrict__
         for (; i + 7 * 16 < n_act; i += 8 * 16) {
             float v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(long)act[i + 16 * u] * C * D];
+            for (int u = 0; u < 8; ++u) v[u] = p[(long)act[i + 16 * u] * pitchC * D];
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc += (double)v[u];
         }
-        for (; i < n_act; i += 16) acc += (double)p[(long)act[i] * C * D];
+        for (; i < n_act; i += 16) acc += (double)p[(long)act[i] * pitchC * D];
     }
     sh[rg][cl] = acc;
     __syncthreads();
@@ -715,9 +716,13 @@ static int proto_blocks(long P) {   // fixed one-round grid; grows only so that 
     const long need = (P + 128 * PR_WPB - 1) / (128 * PR_WPB);
     return (int)(need > PR_BLOCKS ? need : PR_BLOCKS);
 }
+// the streaming kernel keeps one register accumulator per class and is instantiated for 19, 21 and 32 classes: any other
+// C runs the next instantiation up (the extra accumulators stay zero -- no pixel carries their bits -- and the block
+// partials keep that instantiation's [CT][D] pitch, which the finish is told)
+static int proto_ct(int C) { return C <= 19 ? 19 : C <= 21 ? 21 : 32; }
 U2PL_API size_t u2pl_proto_workspace_bytes(long P, int C, int D) {
     const size_t nblk = proto_blocks(P);
-    return nblk * C * D * sizeof(float) + nblk * sizeof(unsigned);
+    return nblk * proto_ct(C) * D * sizeof(float) + nblk * sizeof(unsigned);
 }
 // idx/cap are unused by the streaming formulation (kept in the ABI for list-based callers)
 U2PL_API int u2pl_class_prototypes(const float* rows, long ld, int D, const int* idx, long cap,
@@ -726,23 +731,24 @@ U2PL_API int u2pl_class_prototypes(const float* rows, long ld, int D, const int*
     (void)idx; (void)cap;
     const int nblk = proto_blocks(P);
     const long rb = ((P - 1) * ld + D) * 4;       // byte extent of the row view (raw-buffer descriptor)
-    if (D % 4 || D > 256 || nblk > PF_MAXBLK || P <= 0 || rb >= (1L << 31)) return U2PL_EINVAL;
-    const size_t lds = (size_t)4 * C * D * sizeof(float);
+    if (D % 4 || D > 256 || nblk > PF_MAXBLK || P <= 0 || rb >= (1L << 31) || C <= 0 || C > MAXC) return U2PL_EINVAL;
+    const int CT = proto_ct(C);
+    const size_t lds = (size_t)4 * CT * D * sizeof(float);
     float* partial = (float*)workspace;
-    unsigned* flags = (unsigned*)(partial + (size_t)nblk * C * D);
+    unsigned* flags = (unsigned*)(partial + (size_t)nblk * CT * D);
 #define PROTO_CASE(CT)                                                                                           \
     case CT: {                                                                                                   \
         static bool set_##CT = false;                                                                            \
         if (!set_##CT) { (void)hipFuncSetAttribute((const void*)k_proto_stream<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * CT * 256 * 4)); set_##CT = true; } \
         U2PL_LAUNCH(k_proto_stream<CT>, dim3(nblk), dim3(64 * PR_WPB), lds, stream, rows, ld, D, lowbits, P, partial, flags, (unsigned)rb); \
     } break;
-    switch (C) {
+    switch (CT) {
         PROTO_CASE(19) PROTO_CASE(21) PROTO_CASE(32)
         default: return U2PL_EINVAL;
     }
 #undef PROTO_CASE
     U2PL_LAUNCH_CHECK();
-    U2PL_LAUNCH(k_proto_finish, dim3(C, cdiv(D, 64)), dim3(1024), 0, stream, partial, D, counts, nblk, C, flags, proto);
+    U2PL_LAUNCH(k_proto_finish, dim3(C, cdiv(D, 64)), dim3(1024), 0, stream, partial, D, counts, nblk, CT, flags, proto);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
@@ -1313,12 +1319,27 @@ static int nce_launch(const void* jobs_dev, int njobs, const float* rep, long ld
 U2PL_API size_t u2pl_infonce_job_bytes(void) { return sizeof(NceJob); }
 
 // loss = (sum_jobs mean_q loss_q) / valid_seg = sum_all loss_q / (Q * valid_seg)   (loss_helper.py:228-233)
-// one 1024-thread block, fixed summation order (deterministic), double accumulation
+// one 1024-thread block, fixed summation order (deterministic), double accumulation.  Q % 4 == 0: the arithmetic of the
+// fused launch, operation for operation (fp32 sums of the four anchors a k_infonce block holds, then 256 double accumulators
+// over them with stride 256, a halving tree, one product with inv_valid_seg / Q), so that both forms give the same bits.
 __global__ __launch_bounds__(1024) void k_infonce_reduce(const float* __restrict__ loss_q, int njobs, int Q,
                                                          float inv_valid_seg, float* __restrict__ loss) {
     __shared__ double sh[1024];
     const long n = (long)njobs * Q;
     double acc = 0.0;
+    if (Q % 4 == 0) {
+        if (threadIdx.x < 256)
+            for (long b = threadIdx.x; 4 * b < n; b += 256)
+                acc += (double)((loss_q[4 * b] + loss_q[4 * b + 1]) + (loss_q[4 * b + 2] + loss_q[4 * b + 3]));
+        sh[threadIdx.x] = acc;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) *loss = (float)(sh[0] * ((double)inv_valid_seg / (double)Q));
+        return;
+    }
     for (long i = threadIdx.x; i < n; i += 1024) acc += (double)loss_q[i];
     sh[threadIdx.x] = acc;
     __syncthreads();
