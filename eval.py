@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Evaluation CLI with the reference's surface (eval.py:26-156): --config --model_path --base_size --scales
---save_folder --crop; Cityscapes lists -> sliding-window evaluation, VOC lists -> whole-image evaluation."""
+--save_folder --crop; Cityscapes lists -> sliding-window evaluation, VOC lists -> whole-image evaluation.  Every
+prediction is written to <save_folder>/gray/<name>.png and, in the dataset's colours, <save_folder>/color/<name>.png."""
 import argparse
 import os
 import sys
@@ -44,6 +45,7 @@ def main():
 
     from u2pl_amd import evaluate as E
     from u2pl_amd.engine import load_state
+    from u2pl_amd.infer import colormap
     from u2pl_amd.models.model_helper import ModelBuilder
 
     args = get_parser().parse_args()
@@ -52,13 +54,14 @@ def main():
     mean, std = np.asarray(ds["mean"], np.float32), np.asarray(ds["std"], np.float32)
     classes = cfg["net"]["num_classes"]
     crop = ds["val"]["crop"]["size"]
-    gray = os.path.join(args.save_folder, "gray")
+    gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
     os.makedirs(gray, exist_ok=True)
+    os.makedirs(color, exist_ok=True)
     items = data_list(cfg)
     cfg["net"]["sync_bn"] = False
     model = ModelBuilder(cfg["net"])
     ck = torch.load(args.model_path, map_location="cpu")
-    load_state(args.model_path, model, "teacher_state" if "teacher_state" in ck else "model_state")
+    load_state(args.model_path, model, key="teacher_state" if "teacher_state" in ck else "model_state")
     model = model.cuda()
 
     def samples():
@@ -66,12 +69,15 @@ def main():
             img = (np.asarray(Image.open(ip).convert("RGB")).astype(np.float32) - mean) / std
             yield torch.from_numpy(img).permute(2, 0, 1).contiguous(), np.asarray(Image.open(lp).convert("L")).astype(np.uint8)
 
-    def dump(i, pred):
-        Image.fromarray(pred).save(os.path.join(gray, os.path.basename(items[i][0]).split(".")[0] + ".png"))
+    def dump(i, pred, rgb):
+        name = os.path.basename(items[i][0]).split(".")[0] + ".png"
+        Image.fromarray(pred).save(os.path.join(gray, name))
+        Image.fromarray(rgb).save(os.path.join(color, name))
 
     city = "cityscapes" in ds["type"]
     miou, iou = E.evaluate(model, samples(), classes, args.base_size, crop, args.scales, use_crop=city or args.crop,
-                           ignore=ds.get("ignore_label", 255), on_prediction=dump)
+                           ignore=ds.get("ignore_label", 255), on_prediction=dump,
+                           palette=colormap("cityscapes" if city else "pascal"))
     for c, v in enumerate(iou):
         print(f" * class [{c}] IoU {v * 100:.2f}")
     print(f" * mIoU {miou * 100:.2f}")

@@ -173,6 +173,20 @@ int u2pl_ohem_apply_i64(const float* mask_prob, const unsigned* thr_bits, const 
 int u2pl_confusion_hist_f32(const float* logits_nchw, const long long* target, int ignore, int N, int C, int H, int W,
                             long long* hist3c, hipStream_t stream);
 
+/* ---- infer.hip (prediction epilogue / prologue) ---------------------------- */
+/* F.interpolate(output, (h, w), bilinear, align_corners=True) + torch.argmax(dim=1) + colorful(mask, colormap):
+ * infer.py:127-130,137-142; eval.py:294-300 + utils.py:526-531 (colorize).  The interpolated values are the bits
+ * u2pl_bilinear_up_f32 would store but are never written; lowest class index wins a tie (u2pl_confusion_hist_f32's rule).
+ * label uint8 [N][H][W]; palette uint8 [256][3] and rgb uint8 [N][H][W][3] may both be NULL (labels only).
+ * C > 256 returns 1001. */
+int u2pl_predict_map_f32(const float* in, long sn, long sc, long sh, long sw, int N, int C, int h, int w, int H, int W,
+                         unsigned char* label, const unsigned char* palette, unsigned char* rgb, hipStream_t stream);
+/* (image - mean) / std + permute + F.interpolate(image, input_scale, bilinear, align_corners=True): infer.py:119-124.
+ * img uint8 [h][w][3]; lut float [3][256] = the normalised value of every byte per channel (host: float64 expression
+ * rounded once to fp32); out float [H][W][3], i.e. a (1,3,H,W) tensor in channels_last memory. */
+int u2pl_infer_input_u8_f32(const unsigned char* img_hwc, int h, int w, const float* lut, float* out_hwc, int H, int W,
+                            hipStream_t stream);
+
 /* ---- conv.hip (implicit GEMM on v_mfma_f32_32x32x2_f32) -------------------- */
 /* nn.Conv2d forward (NHWC rows, weights [Cout][R][S][Cin]): resnet.py:25-41,178-186;
  * base.py:23-83; decoder.py:60-106,132-138.  Cin % 32 == 0 (3-channel stem: u2pl_im2col_f32) */

@@ -1,0 +1,60 @@
+#!/usr/bin/env python
+"""Inference CLI with the reference's surface (infer.py:27-134): --config --model_path --save_folder; every image of the
+validation list is resized to the input scale (769 x 769 for Cityscapes, 513 x 513 otherwise, or --input_scale H W),
+run through the network once, and its prediction written to <save_folder>/gray/<file name> (class indices) and
+<save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def get_parser():
+    p = argparse.ArgumentParser(description="U2PL inference (MI355X HIP path)")
+    p.add_argument("--config", type=str, default="config.yaml")
+    p.add_argument("--model_path", type=str, default="checkpoints/psp_best.pth", help="evaluation model path")
+    p.add_argument("--save_folder", type=str, default="viewer", help="results save folder")
+    p.add_argument("--input_scale", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="network input size (default: 769 769 for Cityscapes, else 513 513)")
+    return p
+
+
+def main():
+    from PIL import Image
+    from tqdm import tqdm
+
+    from eval import data_list
+    from u2pl_amd import infer as I
+    from u2pl_amd.engine import load_state
+    from u2pl_amd.models.model_helper import ModelBuilder
+
+    args = get_parser().parse_args()
+    cfg = yaml.load(open(args.config), Loader=yaml.Loader)
+    ds = cfg["dataset"]
+    gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
+    os.makedirs(gray, exist_ok=True)
+    os.makedirs(color, exist_ok=True)
+    items = data_list(cfg)
+    cfg["net"]["sync_bn"] = False
+    model = ModelBuilder(cfg["net"])
+    ck = torch.load(args.model_path, map_location="cpu")
+    load_state(args.model_path, model, key="teacher_state" if "teacher_state" in ck else "model_state")
+    model = model.cuda().eval()
+    input_scale = args.input_scale or ([769, 769] if "cityscapes" in ds["val"]["data_root"] else [513, 513])
+    lut = torch.from_numpy(I.normalise_lut(ds["mean"], ds["std"])).cuda()
+    palette = torch.from_numpy(I.colormap("pascal")).cuda()
+    for image_path, _ in tqdm(items):
+        name = image_path.split("/")[-1]
+        img = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
+        label, rgb, _ = I.infer_image(model, img, lut, input_scale, palette)
+        Image.fromarray(rgb.cpu().numpy()).save(os.path.join(color, name))
+        Image.fromarray(label.cpu().numpy()).save(os.path.join(gray, name))
+
+
+if __name__ == "__main__":
+    main()

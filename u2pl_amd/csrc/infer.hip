@@ -1,0 +1,148 @@
+// Prediction-side kernels (reference infer.py:118-134, eval.py:294-300):
+//   u2pl_infer_input_u8_f32   decoded uint8 image -> normalised, resized network input (channels_last)
+//   u2pl_predict_map_f32      low-resolution logits -> uint8 label map (+ RGB image through a palette)
+// Both use ac_coord and the three-FMA expression of k_bilinear_up (reliability.hip), in that order, so an interpolated
+// value has the bits u2pl_bilinear_up_f32 would have stored; neither writes a full-resolution float tensor per class.
+#include "common.h"
+#include "u2pl_hip.h"
+
+// ---------------------------------------------------------------------------
+// A thread owns 4 consecutive output pixels of one row (one dword of labels, three dwords of RGB); lanes run along the
+// row, so a wave stores 256 contiguous label bytes and 768 contiguous RGB bytes.  Per class it reads the 2 x 2 taps of
+// each pixel from the low-resolution tensor (<= 11 MB: L2 resident, neighbouring pixels share taps in the L1) and
+// keeps the running maximum: classes upward, replaced on strict '>', i.e. the lowest index wins a tie (k_confusion's
+// rule, losses.hip).  A quad whose store address is not dword aligned (W % 4 != 0) or that hangs over the end of the
+// row takes byte stores.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_predict_map(const float* __restrict__ in, long sn, long sc, long sh, long sw, int N, int C, int h, int w, int H, int W,
+              unsigned char* __restrict__ label, const unsigned char* __restrict__ palette, unsigned char* __restrict__ rgb,
+              float sy, float sx) {
+    __shared__ unsigned s_pal[256];   // R | G << 8 | B << 16
+    const bool color = palette != nullptr && rgb != nullptr;
+    if (color) {
+        for (int i = threadIdx.x; i < 256; i += blockDim.x)
+            s_pal[i] = (unsigned)palette[3 * i] | ((unsigned)palette[3 * i + 1] << 8) | ((unsigned)palette[3 * i + 2] << 16);
+        __syncthreads();
+    }
+    const int Wq = (W + 3) >> 2;
+    const long total = (long)N * H * Wq;
+    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+        const int q = (int)(p % Wq);
+        const long t = p / Wq;
+        const int oy = (int)(t % H);
+        const int n = (int)(t / H);
+        const int ox0 = q << 2;
+        const AcCoord cy = ac_coord(oy, sy, h);
+        const long r0 = cy.i0 * sh, r1 = cy.i1 * sh;
+        long c0[4], c1[4];
+        float l0[4], l1[4], best[4];
+        int am[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const AcCoord cx = ac_coord(min(ox0 + j, W - 1), sx, w);   // past the row end: recompute the last pixel, store nothing
+            c0[j] = cx.i0 * sw;
+            c1[j] = cx.i1 * sw;
+            l0[j] = cx.l0;
+            l1[j] = cx.l1;
+            am[j] = 0;
+            best[j] = 0.f;
+        }
+        const float* b = in + n * sn;
+        for (int c = 0; c < C; ++c) {
+            const float* t0 = b + c * sc + r0;
+            const float* t1 = b + c * sc + r1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float top = __fmaf_rn(l0[j], t0[c0[j]], __fmul_rn(l1[j], t0[c1[j]]));
+                const float bot = __fmaf_rn(l0[j], t1[c0[j]], __fmul_rn(l1[j], t1[c1[j]]));
+                const float v = __fmaf_rn(cy.l0, top, __fmul_rn(cy.l1, bot));
+                if (c == 0) best[j] = v;
+                else if (v > best[j]) { best[j] = v; am[j] = c; }
+            }
+        }
+        const long px = ((long)n * H + oy) * W + ox0;
+        const bool full = ox0 + 4 <= W;
+        unsigned char* lp = label + px;
+        if (full && ((uintptr_t)lp & 3) == 0) {
+            *(unsigned*)lp = (unsigned)am[0] | ((unsigned)am[1] << 8) | ((unsigned)am[2] << 16) | ((unsigned)am[3] << 24);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (ox0 + j < W) lp[j] = (unsigned char)am[j];
+        }
+        if (color) {
+            const unsigned p0 = s_pal[am[0]], p1 = s_pal[am[1]], p2 = s_pal[am[2]], p3 = s_pal[am[3]];
+            unsigned char* cp = rgb + 3 * px;
+            if (full && ((uintptr_t)cp & 3) == 0) {
+                unsigned* d = (unsigned*)cp;
+                d[0] = p0 | (p1 << 24);
+                d[1] = (p1 >> 8) | (p2 << 16);
+                d[2] = (p2 >> 16) | (p3 << 8);
+            } else {
+                const unsigned pp[4] = {p0, p1, p2, p3};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (ox0 + j < W) {
+                        cp[3 * j] = (unsigned char)pp[j];
+                        cp[3 * j + 1] = (unsigned char)(pp[j] >> 8);
+                        cp[3 * j + 2] = (unsigned char)(pp[j] >> 16);
+                    }
+            }
+        }
+    }
+}
+
+U2PL_API int u2pl_predict_map_f32(const float* in, long sn, long sc, long sh, long sw, int N, int C, int h, int w, int H,
+                                  int W, unsigned char* label, const unsigned char* palette, unsigned char* rgb,
+                                  hipStream_t stream) {
+    if (C > 256 || h < 1 || w < 1 || H < 0 || W < 0 || !in || !label) return U2PL_EINVAL;   // a label is one byte
+    if (N <= 0 || C <= 0 || H == 0 || W == 0) return 0;
+    const long total = (long)N * H * ((W + 3) >> 2);
+    U2PL_LAUNCH(k_predict_map, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, stream, in, sn, sc, sh, sw, N, C, h, w, H,
+                W, label, palette, rgb, ac_scale_host(h, H), ac_scale_host(w, W));
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// out[oy][ox][c] = bilinear(align_corners=True) of lut[c][img[y][x][c]]: the normalisation is a gather from a table the
+// host fills ((v - mean) / std evaluated in float64 and rounded once, as the reference's numpy expression does), so
+// the kernel holds no arithmetic of its own besides the interpolation.  One thread per output pixel: 12 contiguous
+// bytes per lane.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_infer_input(const unsigned char* __restrict__ img, int h, int w, const float* __restrict__ lut, float* __restrict__ out,
+              int H, int W, float sy, float sx) {
+    __shared__ float s_lut[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += blockDim.x) s_lut[i] = lut[i];
+    __syncthreads();
+    const long total = (long)H * W;
+    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+        const int ox = (int)(p % W), oy = (int)(p / W);
+        const AcCoord cy = ac_coord(oy, sy, h), cx = ac_coord(ox, sx, w);
+        const unsigned char* p00 = img + 3 * ((long)cy.i0 * w + cx.i0);
+        const unsigned char* p01 = img + 3 * ((long)cy.i0 * w + cx.i1);
+        const unsigned char* p10 = img + 3 * ((long)cy.i1 * w + cx.i0);
+        const unsigned char* p11 = img + 3 * ((long)cy.i1 * w + cx.i1);
+        float* o = out + 3 * p;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* l = s_lut + 256 * c;
+            const float top = __fmaf_rn(cx.l0, l[p00[c]], __fmul_rn(cx.l1, l[p01[c]]));
+            const float bot = __fmaf_rn(cx.l0, l[p10[c]], __fmul_rn(cx.l1, l[p11[c]]));
+            o[c] = __fmaf_rn(cy.l0, top, __fmul_rn(cy.l1, bot));
+        }
+    }
+}
+
+U2PL_API int u2pl_infer_input_u8_f32(const unsigned char* img_hwc, int h, int w, const float* lut, float* out_hwc, int H,
+                                     int W, hipStream_t stream) {
+    if (h < 1 || w < 1 || H < 0 || W < 0 || !img_hwc || !lut || !out_hwc) return U2PL_EINVAL;
+    const long total = (long)H * W;
+    if (total == 0) return 0;
+    U2PL_LAUNCH(k_infer_input, dim3(grid_for(total, 256)), dim3(256), 0, stream, img_hwc, h, w, lut, out_hwc, H, W,
+                ac_scale_host(h, H), ac_scale_host(w, W));
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}

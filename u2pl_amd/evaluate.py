@@ -87,19 +87,27 @@ def predict_image(model, image, classes, base_size, crop, scales=(1.0,), use_cro
 
 
 @torch.no_grad()
-def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=True, ignore=255, on_prediction=None):
+def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=True, ignore=255, on_prediction=None,
+             palette=None):
     """samples: iterable of (image (3,h,w) float tensor already mean/std normalised, label (h,w) integer array).
-    Returns (mIoU, per-class IoU).  on_prediction(i, uint8 map) receives every argmax map (gray / colour dumps)."""
+    Returns (mIoU, per-class IoU).  on_prediction(i, uint8 map) receives every argmax map (gray dumps); with a
+    palette ((256,3) uint8, array or tensor) it is called as on_prediction(i, gray, color): both maps come from one
+    u2pl_predict_map_f32 launch on the summed logits (lowest class index wins a tie) and one uint8 copy each."""
     model.eval()
     dev = next(model.parameters()).device
     hist = torch.zeros(3 * classes, dtype=torch.int64, device=dev)
+    if palette is not None:
+        palette = torch.as_tensor(palette).to(dev)
     for i, (image, label) in enumerate(samples):
         image = torch.as_tensor(image, dtype=torch.float32).unsqueeze(0).to(dev)
         logits = predict_image(model, image, classes, base_size, crop, scales, use_crop)
         lab = torch.as_tensor(np.asarray(label)).to(dev).long().contiguous().unsqueeze(0)
         h, w = lab.shape[1:]
         call("u2pl_confusion_hist_f32", logits.contiguous(), lab, ignore, 1, classes, h, w, hist)
-        if on_prediction is not None:
+        if on_prediction is not None and palette is not None:
+            gray, color = H.predict_map(logits.unsqueeze(0), (h, w), palette)
+            on_prediction(i, gray[0].cpu().numpy(), color[0].cpu().numpy())
+        elif on_prediction is not None:
             on_prediction(i, logits.argmax(0).to(torch.uint8).cpu().numpy())
     hh = hist.cpu().double().reshape(3, classes)
     inter, union = hh[0], hh[1] + hh[2] - hh[0]

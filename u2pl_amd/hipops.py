@@ -58,6 +58,47 @@ def bilinear_up(x, size):
     return _BilinearUp.apply(x, int(size[0]), int(size[1]))
 
 
+# --------------------------------------------------------------------------- prediction maps (infer.py, eval.py dumps)
+def _u8c(x, what):
+    if x.dtype != torch.uint8:
+        raise _lib.HipError(f"{what}: expected a uint8 tensor")
+    return x.contiguous()
+
+
+def predict_map(logits_low, size, palette=None):
+    """argmax_c F.interpolate(logits_low, size, 'bilinear', align_corners=True) -> (label uint8 (N,H,W), rgb uint8
+    (N,H,W,3) = palette[label] or None); the (N,C,H,W) logits are never written.  logits_low may be any strided
+    (N,C,h,w) view; palette: (256,3) uint8 on the same device.  Lowest class index wins a tie."""
+    _chk_cuda(logits_low, palette)
+    N, C, h, w = logits_low.shape
+    H, W = int(size[0]), int(size[1])
+    label = torch.empty((N, H, W), dtype=torch.uint8, device=logits_low.device)
+    rgb = None
+    if palette is not None:
+        if tuple(palette.shape) != (256, 3):
+            raise _lib.HipError("palette: expected shape (256, 3)")
+        palette = _u8c(palette, "palette")
+        rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=logits_low.device)
+    call("u2pl_predict_map_f32", _f32c(logits_low), *_strides_nchw(logits_low), N, C, h, w, H, W, label, palette, rgb)
+    return label, rgb
+
+
+def infer_input(img_u8_hwc, lut, size):
+    """decoded image (h,w,3) uint8 -> network input (1,3,H,W) float32 in channels_last memory: lut[c][byte]
+    (infer.normalise_lut) then bilinear(align_corners=True) to `size`, in one kernel."""
+    _chk_cuda(img_u8_hwc, lut)
+    if img_u8_hwc.dim() != 3 or img_u8_hwc.shape[2] != 3:
+        raise _lib.HipError("infer_input: expected an (h, w, 3) image")
+    if tuple(lut.shape) != (3, 256):
+        raise _lib.HipError("infer_input: expected a (3, 256) table")
+    img = _u8c(img_u8_hwc, "infer_input")
+    h, w = img.shape[:2]
+    H, W = int(size[0]), int(size[1])
+    out = torch.empty((1, 3, H, W), dtype=torch.float32, device=img.device, memory_format=torch.channels_last)
+    call("u2pl_infer_input_u8_f32", img, h, w, _f32c(lut).contiguous(), out, H, W)
+    return out
+
+
 # --------------------------------------------------------------------------- pseudo label
 def pseudo_label(logits_large):
     """softmax + max over classes (train_semi.py:323-324) -> (conf, label int64)."""

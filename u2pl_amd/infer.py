@@ -1,0 +1,52 @@
+"""Single-image inference (reference infer.py:111-134) and the colour maps of the gray / colour dumps
+(utils.py:526-531, 639-700) on the HIP path.
+
+  normalise_lut   infer.py:119-121   (image - mean) / std as a per-channel table over the 256 byte values
+  infer_image     infer.py:118-130   table gather + bilinear to the input scale (one kernel), forward, then bilinear to
+                                     the image size + argmax + colour lookup (one kernel): neither the resized float
+                                     image on the host nor the full-resolution logits exist
+  colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables
+"""
+import numpy as np
+import torch
+
+from . import hipops as H
+
+# the 19 Cityscapes train ids (road ... bicycle) in the colours of the official cityscapesScripts label table
+_CITYSCAPES = [(128, 64, 128), (244, 35, 232), (70, 70, 70), (102, 102, 156), (190, 153, 153), (153, 153, 153), (250, 170, 30),
+               (220, 220, 0), (107, 142, 35), (152, 251, 152), (70, 130, 180), (220, 20, 60), (255, 0, 0), (0, 0, 142), (0, 0, 70),
+               (0, 60, 100), (0, 80, 100), (0, 0, 230), (119, 11, 32)]
+
+
+def colormap(name):
+    """(256, 3) uint8 table of `name` ("pascal" | "cityscapes").  Pascal: the VOC devkit's rule for classes 0..20 (bit
+    3j + k of the class index becomes bit 7 - j of channel k), every other row 255; Cityscapes: the 19 train-id colours,
+    every other row 0 -- the rows the reference's tables leave at their fill value."""
+    if name == "pascal":
+        cm = np.full((256, 3), 255, np.uint8)
+        for i in range(21):
+            cm[i] = [sum(((i >> (3 * j + k)) & 1) << (7 - j) for j in range(3)) for k in range(3)]
+        return cm
+    if name == "cityscapes":
+        cm = np.zeros((256, 3), np.uint8)
+        cm[:len(_CITYSCAPES)] = _CITYSCAPES
+        return cm
+    raise ValueError(f"unknown colour map {name!r}")
+
+
+def normalise_lut(mean, std):
+    """(3, 256) float32: [c][v] = (v - mean[c]) / std[c].  As in the reference the byte value is a float32 and mean / std
+    are Python lists, so numpy evaluates the expression in float64; the result is rounded to float32 once."""
+    v = np.arange(256, dtype=np.float32)[:, None]
+    return np.ascontiguousarray(((v - list(mean)) / list(std)).astype(np.float32).T)
+
+
+@torch.no_grad()
+def infer_image(model, img_u8, lut, input_scale, palette=None):
+    """img_u8 (h,w,3) uint8, lut (3,256) float32, palette (256,3) uint8 or None: GPU tensors.
+    -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits)."""
+    h, w = img_u8.shape[:2]
+    x = H.infer_input(img_u8, lut, input_scale)
+    pred = model(x, need_aux=False, need_rep=False)["pred"]
+    label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
+    return label[0], None if rgb is None else rgb[0], pred
