@@ -274,6 +274,28 @@ int u2pl_wgrad_set_tr(int on);
 int u2pl_im2col_f32(const float* x, long ldx, float* col, int Kp, int N, int Hin, int Win, int Cin, int Hout,
                     int Wout, int R, int S, int stride, int pad, int dil, hipStream_t stream);
 
+/* ---- gconv.hip (grouped convolution in exact fp32 on v_mfma_f32_16x16x4_f32) -------------------------------------
+ * nn.Conv2d(groups > 1): the 3x3 of a ResNeXt bottleneck, resnet.py:25-36 (conv3x3 with groups) / :108-112 (Bottleneck width
+ * and conv2).  Rows as in conv.hip (x / y / dy / dx are [N*H*W][ld], ld >= C: channel slices of wider buffers work); w is the
+ * module's weight (Cout, Cin/groups, R, S) stored channels_last = [Cout][R][S][Cin/groups] -- the data gradient reads the SAME
+ * tensor (no transposed or split operand).  Constraints (U2PL_EINVAL before any launch otherwise): Cin and Cout divisible by
+ * groups; Cin/groups and Cout/groups multiples of 4 up to 64; stride 1 or 2; any dilation; R * S < 128, S <= 16; Hout / Wout the
+ * convolution's output size; pointers 16-byte aligned and ld % 4 == 0.  fp32 products, fp32 accumulation, no atomics: the
+ * weight gradient sums its pixel slabs in slab order, two runs give the same bits. */
+/* forward (resnet.py:25-36, :108-112), bias optional (NULL) */
+int u2pl_gconv2d_fwd_f32(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, int N, int Hin,
+                         int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                         int groups, hipStream_t stream);
+/* autograd of that layer under loss.backward() (resnet.py:25-36, :108-112; train_semi.py:527): data gradient, stride 2 included */
+int u2pl_gconv2d_dgrad_f32(const float* dy, long lddy, const float* w, float* dx, long lddx, int N, int Hin, int Win,
+                           int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil, int groups,
+                           hipStream_t stream);
+/* weight gradient of that layer (resnet.py:25-36, :108-112): workspace = per-slab partial sums; accumulate: dw += instead of dw = */
+size_t u2pl_gconv2d_wgrad_workspace_bytes(int N, int Hout, int Wout, int Cin, int Cout, int R, int S, int groups);
+int u2pl_gconv2d_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, float* dw, void* workspace,
+                           int accumulate, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
+                           int S, int stride, int pad, int dil, int groups, hipStream_t stream);
+
 /* ---- igemm_ws.hip (split-fp32 implicit GEMM with pre-split weights; round 4) -------------------------------------
  * The weights of the network change once per optimizer step (train_semi.py:526-528 optimizer.step(), :531-548 the EMA
  * teacher), the convolutions read them ~14 times per step (resnet.py:120-140 through the two student and two teacher

@@ -14,8 +14,8 @@ model_urls = {k: f"/path/to/{k}.pth" for k in ["resnet18", "resnet34", "resnet50
 
 
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
-    assert groups == 1
-    return K.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, dilation=dilation, bias=False)
+    return K.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, dilation=dilation, bias=False,
+                    groups=groups)
 
 
 def conv1x1(in_planes, out_planes, stride=1):

@@ -458,6 +458,8 @@ def residual_grad_link(x):
 
 def dgrad_fusable(conv, x):
     """does this conv's data gradient have a fused accumulate form (pointwise stride-1 on the pre-split kernels, or Winograd)?"""
+    if conv.groups != 1:        # (csrc/gconv.hip's data gradient has no accumulate form)
+        return False
     Cout, Cin, R, S = conv.weight.shape
     H, W = x.shape[2], x.shape[3]
     if R == 1 and S == 1 and conv.stride == 1 and conv.padding == 0:
@@ -465,19 +467,117 @@ def dgrad_fusable(conv, x):
     return bool(wino_tile(Cout, Cin, R, S, conv.stride, conv.padding, conv.dilation, H, W)) and Cout % 32 == 0 and Cin % 4 == 0
 
 
-class Conv2d(nn.Module):
-    """nn.Conv2d(groups=1) with torch's default init, weight stored channels_last."""
+def gconv_constraint(Cin, Cout, groups, stride):
+    """-> None, or the constraint of csrc/gconv.hip that a grouped convolution of this shape breaks (the text of the HipError)"""
+    if groups < 1 or Cin % groups or Cout % groups:
+        return "in_channels (%d) and out_channels (%d) must be divisible by groups (%d)" % (Cin, Cout, groups)
+    cig, cog = Cin // groups, Cout // groups
+    if cig % 4 or cog % 4 or cig > 64 or cog > 64:
+        return ("channels per group must be a multiple of 4 up to 64, got in %d / out %d (groups=%d; depthwise and odd widths "
+                "are not supported)" % (cig, cog, groups))
+    if stride not in (1, 2):
+        return "stride must be 1 or 2, got %d" % stride
+    return None
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True):
+
+class _GroupedConvFn(torch.autograd.Function):
+    """nn.Conv2d(groups > 1) on csrc/gconv.hip: exact fp32, all three kernels read the module's own weight tensor (no derived
+    operand, so nothing for presplit() / the graph capture's "operand must be current" rule).  Same contracts as _ConvFn:
+    arena gradient sinks + _mark_ready, GradJoin on the input, weight gradient on the side stream."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, dil, groups, wsink, bsink, link=None):
+        x, ldx = as_rows(x)
+        N, Cin, H, W = x.shape
+        Cout, cig, R, S = weight.shape
+        why = gconv_constraint(Cin, Cout, groups, stride)
+        if why is None and cig * groups != Cin:
+            why = "weight has %d input channels per group, the input %d channels in %d groups" % (cig, Cin, groups)
+        if why is not None:
+            raise HipError("grouped convolution: " + why)
+        if not weight.is_contiguous(memory_format=_CL) and not (R == 1 and S == 1 and weight.is_contiguous()):
+            raise HipError("conv weight must be stored channels_last ([Cout][R][S][Cin/groups])")
+        Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
+        Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+        ctx.set_materialize_grads(False)
+        ctx.link = link
+        y = new_act(N, Cout, Ho, Wo, x.device)
+        call("u2pl_gconv2d_fwd_f32", x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
+        ctx.save_for_backward(x, weight)
+        ctx.geom = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups, ldx)
+        ctx.has_bias = bias is not None
+        ctx.wsink, ctx.bsink = wsink, bsink
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return (None,) * 10
+        x, weight = ctx.saved_tensors
+        N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups, ldx = ctx.geom
+        gy, ldg = as_rows(gy)
+        dev = gy.device
+        M = N * Ho * Wo
+        dx = dw = db = None
+        join = ctx.link
+        if join is not None and not ctx.needs_input_grad[0]:
+            raise HipError("gradient join on a convolution whose input needs no gradient")
+        if ctx.needs_input_grad[0]:
+            dx = new_act(N, Cin, H, W, dev)
+            call("u2pl_gconv2d_dgrad_f32", gy, ldg, weight, dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
+            if join is not None:
+                dx = join.settle(dx, False)         # (no fused accumulate form: the running sum is added in place)
+        side = _wgrad_stream() if (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) else None
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+            _lib.SIDE_WORK.add("wgrad")
+            gy.record_stream(side)
+            x.record_stream(side)
+            _queue_wgrad_join()
+            stream_ctx = torch.cuda.stream(side)
+            stream_ctx.__enter__()
+        if ctx.needs_input_grad[1]:
+            sink = ctx.wsink
+            wsb = _ws(query("u2pl_gconv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups), dev)
+            tgt = sink if sink is not None else torch.empty_like(weight)
+            call("u2pl_gconv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb, int(sink is not None), N, H, W, Cin, Ho, Wo, Cout, R, S, stride,
+                 pad, dil, groups)
+            if sink is None:
+                dw = tgt
+            _mark_ready(sink)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
+            wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, Cout), dev)
+            call("u2pl_colsum_f32", gy, ldg, M, 1, Cout, wsb, sums)
+            if ctx.bsink is not None:
+                call("u2pl_sums_to_f32", sums, Cout, 1.0, 1, ctx.bsink)
+                _mark_ready(ctx.bsink)
+            else:
+                db = torch.empty(Cout, dtype=torch.float32, device=dev)
+                call("u2pl_sums_to_f32", sums, Cout, 1.0, 0, db)
+        if side is not None:
+            stream_ctx.__exit__(None, None, None)
+            if dw is not None or db is not None:    # returned to autograd on the main stream
+                torch.cuda.current_stream().wait_stream(side)
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+class Conv2d(nn.Module):
+    """nn.Conv2d with torch's default init, weight stored channels_last.  groups > 1 (the 3x3 of a ResNeXt bottleneck) runs on
+    csrc/gconv.hip (_GroupedConvFn); the shape constraints of that route are reported at the first call, not at construction."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, groups=1):
         super().__init__()
         k = kernel_size
-        self.in_channels, self.out_channels = in_channels, out_channels
+        if groups < 1 or in_channels % groups or out_channels % groups:      # (torch.nn.Conv2d's own construction errors)
+            raise ValueError("in_channels and out_channels must be divisible by groups")
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
         self.kernel_size, self.stride, self.padding, self.dilation = (k, k), stride, padding, dilation
-        w = torch.empty(out_channels, in_channels, k, k)
+        w = torch.empty(out_channels, in_channels // groups, k, k)
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))  # == nn.Conv2d.reset_parameters (same RNG draws)
         self.weight = nn.Parameter(w.contiguous(memory_format=_CL))
         if bias:
-            fan_in = in_channels * k * k
+            fan_in = (in_channels // groups) * k * k
             bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
             b = torch.empty(out_channels)
             nn.init.uniform_(b, -bound, bound)
@@ -488,13 +588,18 @@ class Conv2d(nn.Module):
     def forward(self, x, stat_pivot=None, grad_link=None):
         """stat_pivot: running_mean of a following train-mode BatchNorm -> returns (y, fused BN sums).
         grad_link: a GradJoin shared with the other consumers of x (grad_join)."""
+        if self.groups != 1:
+            y = _GroupedConvFn.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups,
+                                     _grad_sink(self.weight), _grad_sink(self.bias) if self.bias is not None else None, grad_link)
+            return y if stat_pivot is None else (y, None)     # statistics by the stand-alone pass (_bn_local_sums)
         out = _ConvFn.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation,
                             _grad_sink(self.weight), _grad_sink(self.bias) if self.bias is not None else None, stat_pivot,
                             torch.is_grad_enabled(), grad_link)
         return out
 
     def extra_repr(self):
-        return f"{self.in_channels}, {self.out_channels}, k={self.kernel_size}, s={self.stride}, p={self.padding}, d={self.dilation}"
+        s = f"{self.in_channels}, {self.out_channels}, k={self.kernel_size}, s={self.stride}, p={self.padding}, d={self.dilation}"
+        return s if self.groups == 1 else s + f", g={self.groups}"
 
 
 # ------------------------------------------------------------------ batch norm (+res +relu +dropout)
@@ -990,7 +1095,7 @@ def conv_bn(conv, bn, x, res=None, relu=False, drop=None, grad_link=None, res_li
     """conv -> BatchNorm (+residual, ReLU, Dropout2d scale).  In training mode the BN statistics are
     produced by the conv kernel's epilogue (no separate read pass over the conv output); in eval mode without a
     recorded graph the whole BatchNorm runs in the conv's epilogue (conv_bn_eval)."""
-    if (FUSE_EVAL_BN and not bn.training and drop is None
+    if (FUSE_EVAL_BN and not bn.training and drop is None and conv.groups == 1     # (conv_bn_eval assumes a dense weight)
             and not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or bn.weight.requires_grad))):
         y = conv_bn_eval(conv, bn, x, res=res, relu=relu)
         if y is not None:
