@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Evaluation CLI with the reference's surface (eval.py:26-156): --config --model_path --base_size --scales
 --save_folder --crop; Cityscapes lists -> sliding-window evaluation, VOC lists -> whole-image evaluation.  Every
-prediction is written to <save_folder>/gray/<name>.png and, in the dataset's colours, <save_folder>/color/<name>.png."""
+prediction is written to <save_folder>/gray/<name>.png and, in the dataset's colours, <save_folder>/color/<name>.png.
+--half (this project's option): the forward passes on the fp16 path."""
 import argparse
 import os
 import sys
@@ -22,6 +23,15 @@ def get_parser():
     p.add_argument("--save_folder", type=str, default="checkpoints/results/")
     p.add_argument("--names_path", type=str, default="")
     p.add_argument("--crop", action="store_true", default=False)
+    return p
+
+
+def get_cli_parser():
+    """get_parser() keeps the reference's surface; the options only this project has are added here"""
+    p = get_parser()
+    p.add_argument("--half", action="store_true", default=False,
+                   help="forward passes with fp16 activations and weights (u2pl_amd.half); a pass that saturates is "
+                        "recomputed in fp32")
     return p
 
 
@@ -48,7 +58,7 @@ def main():
     from u2pl_amd.infer import colormap
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_parser().parse_args()
+    args = get_cli_parser().parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     mean, std = np.asarray(ds["mean"], np.float32), np.asarray(ds["std"], np.float32)
@@ -63,6 +73,10 @@ def main():
     ck = torch.load(args.model_path, map_location="cpu")
     load_state(args.model_path, model, key="teacher_state" if "teacher_state" in ck else "model_state")
     model = model.cuda()
+    half = None
+    if args.half:
+        from u2pl_amd.half import HalfPredictor
+        half = HalfPredictor(model.eval())
 
     def samples():
         for ip, lp in items:
@@ -77,10 +91,12 @@ def main():
     city = "cityscapes" in ds["type"]
     miou, iou = E.evaluate(model, samples(), classes, args.base_size, crop, args.scales, use_crop=city or args.crop,
                            ignore=ds.get("ignore_label", 255), on_prediction=dump,
-                           palette=colormap("cityscapes" if city else "pascal"))
+                           palette=colormap("cityscapes" if city else "pascal"), half=half)
     for c, v in enumerate(iou):
         print(f" * class [{c}] IoU {v * 100:.2f}")
     print(f" * mIoU {miou * 100:.2f}")
+    if half is not None:
+        print(half.log_line())
 
 
 if __name__ == "__main__":

@@ -568,6 +568,36 @@ int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned char* lab, c
                            const float* mean3, const float* std3, const float* blur_w, float* scratch, float* out_img,
                            long long* out_lab, hipStream_t stream);
 
+/* ---- fp16 prediction path (csrc/half.hip): eval-mode forward with fp16 activations and weights.
+   Activations are NHWC rows of IEEE fp16 (unsigned short bit patterns) with a pitch in elements; gfx950 only. ---- */
+/* fp32 [Cout][Cin][R][S] -> fp16 [Cout][R][S][Cin], round to nearest even (BatchNorm is NOT folded in) */
+int u2pl_half_weight_f16(const float* w, int Cout, int Cin, int R, int S, unsigned short* out, hipStream_t stream);
+/* dense convolution, implicit GEMM on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  x: pitch ldx >= Cin (a multiple
+   of 8, base 16-byte aligned), Cin % 32 == 0; w from u2pl_half_weight_f16; any R x S, stride, pad, dil (Hout / Wout are
+   checked against them).  Epilogue in fp32: v = acc * scale[c] + shift[c] (scale NULL: 1, shift NULL: 0), + res (fp16,
+   pitch ldr, NULL: none), ReLU (relu != 0), then ONE rounding to fp16 into y (pitch ldy >= Cout: a channel slice of a
+   concat buffer), or out_f32 != 0: y is float with pitch ldy and nothing is rounded.  A value with |v| > 65504 is stored
+   as +-65504 and *sat (int32, device, zeroed by the caller; NULL: not counted) is incremented.  tile: 0 = the launcher
+   chooses 64 or 128 pixel rows per block, 1 / 2 force one (tests). */
+int u2pl_hconv2d_fwd_f16(const unsigned short* x, long ldx, const unsigned short* w, const float* scale,
+                         const float* shift, const unsigned short* res, long ldr, void* y, long ldy, int N, int Hin,
+                         int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                         int relu, int out_f32, int tile, int* sat, hipStream_t stream);
+/* direct form for a few input channels (the stem: Cin = 3): x is the fp32 NHWC image (u2pl_infer_input_u8_f32's
+   layout), R * S * Cin * Cout <= 8192; same epilogue without a residual, fp16 output */
+int u2pl_hconv2d_stem_f16(const float* x, long ldx, const unsigned short* w, const float* scale, const float* shift,
+                          unsigned short* y, long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
+                          int R, int S, int stride, int pad, int dil, int relu, int* sat, hipStream_t stream);
+/* MaxPool2d(3, 2, 1, ceil_mode=True); C % 8 == 0, pitches multiples of 8, bases 16-byte aligned */
+int u2pl_hmaxpool3s2_f16(const unsigned short* x, long ldx, int N, int H, int W, int C, int Ho, int Wo,
+                         unsigned short* y, long ldy, hipStream_t stream);
+/* y [N][C] = fp16(mean over the HW pixels of x [N][HW] rows), fp32 sums in a fixed order */
+int u2pl_hgap_f16(const unsigned short* x, long ldx, int N, int HW, int C, unsigned short* y, hipStream_t stream);
+/* bilinear, align_corners=True, [N][h][w] rows -> [N][H][W] rows with pitch ldy: ac_coord and the three-FMA expression
+   of u2pl_bilinear_up_f32 on the widened taps, one rounding; C % 8 == 0, pitches multiples of 8, 16-byte bases */
+int u2pl_hbilinear_f16(const unsigned short* x, long ldx, int N, int h, int w, int C, unsigned short* y, long ldy,
+                       int H, int W, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

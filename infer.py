@@ -2,7 +2,8 @@
 """Inference CLI with the reference's surface (infer.py:27-134): --config --model_path --save_folder; every image of the
 validation list is resized to the input scale (769 x 769 for Cityscapes, 513 x 513 otherwise, or --input_scale H W),
 run through the network once, and its prediction written to <save_folder>/gray/<file name> (class indices) and
-<save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14)."""
+<save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14).  --half (this project's
+option): the forward pass on the fp16 path."""
 import argparse
 import os
 import sys
@@ -24,6 +25,15 @@ def get_parser():
     return p
 
 
+def get_cli_parser():
+    """get_parser() keeps the reference's surface; the options only this project has are added here"""
+    p = get_parser()
+    p.add_argument("--half", action="store_true", default=False,
+                   help="forward pass with fp16 activations and weights (u2pl_amd.half); an image whose pass saturates is "
+                        "run again in fp32")
+    return p
+
+
 def main():
     from PIL import Image
     from tqdm import tqdm
@@ -33,7 +43,7 @@ def main():
     from u2pl_amd.engine import load_state
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_parser().parse_args()
+    args = get_cli_parser().parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
@@ -48,12 +58,18 @@ def main():
     input_scale = args.input_scale or ([769, 769] if "cityscapes" in ds["val"]["data_root"] else [513, 513])
     lut = torch.from_numpy(I.normalise_lut(ds["mean"], ds["std"])).cuda()
     palette = torch.from_numpy(I.colormap("pascal")).cuda()
+    half = None
+    if args.half:
+        from u2pl_amd.half import HalfPredictor
+        half = HalfPredictor(model)
     for image_path, _ in tqdm(items):
         name = image_path.split("/")[-1]
         img = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
-        label, rgb, _ = I.infer_image(model, img, lut, input_scale, palette)
+        label, rgb = I.infer_image(model, img, lut, input_scale, palette, half=half)[:2]
         Image.fromarray(rgb.cpu().numpy()).save(os.path.join(color, name))
         Image.fromarray(label.cpu().numpy()).save(os.path.join(gray, name))
+    if half is not None:
+        print(half.log_line())
 
 
 if __name__ == "__main__":

@@ -4,7 +4,8 @@
   normalise_lut   infer.py:119-121   (image - mean) / std as a per-channel table over the 256 byte values
   infer_image     infer.py:118-130   table gather + bilinear to the input scale (one kernel), forward, then bilinear to
                                      the image size + argmax + colour lookup (one kernel): neither the resized float
-                                     image on the host nor the full-resolution logits exist
+                                     image on the host nor the full-resolution logits exist; half=: the forward on the
+                                     fp16 path (u2pl_amd.half), redone in fp32 when it saturated
   colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables
 """
 import numpy as np
@@ -42,11 +43,20 @@ def normalise_lut(mean, std):
 
 
 @torch.no_grad()
-def infer_image(model, img_u8, lut, input_scale, palette=None):
+def infer_image(model, img_u8, lut, input_scale, palette=None, half=None):
     """img_u8 (h,w,3) uint8, lut (3,256) float32, palette (256,3) uint8 or None: GPU tensors.
-    -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits)."""
+    -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits).
+    half: a u2pl_amd.half.HalfPredictor of `model` -- the forward pass runs with fp16 activations and weights, and the
+    result gains a fourth element, fell_back: True when that pass saturated (a stored activation beyond +-65504) and the
+    image was therefore run again on the fp32 path, whose result is then what is returned."""
     h, w = img_u8.shape[:2]
     x = H.infer_input(img_u8, lut, input_scale)
-    pred = model(x, need_aux=False, need_rep=False)["pred"]
+    fell_back = False
+    if half is not None:
+        pred, saturated = half(x)
+        fell_back = saturated > 0
+    if half is None or fell_back:
+        pred = model(x, need_aux=False, need_rep=False)["pred"]
     label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
-    return label[0], None if rgb is None else rgb[0], pred
+    out = (label[0], None if rgb is None else rgb[0], pred)
+    return out if half is None else out + (fell_back,)
