@@ -2,7 +2,8 @@
 """Evaluation CLI with the reference's surface (eval.py:26-156): --config --model_path --base_size --scales
 --save_folder --crop; Cityscapes lists -> sliding-window evaluation, VOC lists -> whole-image evaluation.  Every
 prediction is written to <save_folder>/gray/<name>.png and, in the dataset's colours, <save_folder>/color/<name>.png.
---half (this project's option): the forward passes on the fp16 path."""
+This project's options: --half, the forward passes on the fp16 path; --flip / --prob, test-time fusion of every
+window (a mirrored view, class probabilities instead of logits) -- with --scales this is "ms+flip"."""
 import argparse
 import os
 import sys
@@ -26,12 +27,19 @@ def get_parser():
     return p
 
 
-def get_cli_parser():
-    """get_parser() keeps the reference's surface; the options only this project has are added here"""
+def get_cli_parser(fusion=False):
+    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, and with
+    fusion=True (what main() parses) the test-time fusion options --flip and --prob"""
     p = get_parser()
     p.add_argument("--half", action="store_true", default=False,
                    help="forward passes with fp16 activations and weights (u2pl_amd.half); a pass that saturates is "
                         "recomputed in fp32")
+    if not fusion:
+        return p
+    p.add_argument("--flip", action="store_true", default=False,
+                   help="test-time flip: every window also runs mirrored, the result is mirrored back and the two are averaged")
+    p.add_argument("--prob", action="store_true", default=False,
+                   help="fuse class probabilities (softmax per view) instead of raw logits, per window and scale")
     return p
 
 
@@ -58,7 +66,7 @@ def main():
     from u2pl_amd.infer import colormap
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_cli_parser().parse_args()
+    args = get_cli_parser(fusion=True).parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     mean, std = np.asarray(ds["mean"], np.float32), np.asarray(ds["std"], np.float32)
@@ -91,7 +99,8 @@ def main():
     city = "cityscapes" in ds["type"]
     miou, iou = E.evaluate(model, samples(), classes, args.base_size, crop, args.scales, use_crop=city or args.crop,
                            ignore=ds.get("ignore_label", 255), on_prediction=dump,
-                           palette=colormap("cityscapes" if city else "pascal"), half=half)
+                           palette=colormap("cityscapes" if city else "pascal"), half=half, flip=args.flip,
+                           prob=args.prob)
     for c, v in enumerate(iou):
         print(f" * class [{c}] IoU {v * 100:.2f}")
     print(f" * mIoU {miou * 100:.2f}")

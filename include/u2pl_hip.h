@@ -186,6 +186,15 @@ int u2pl_predict_map_f32(const float* in, long sn, long sc, long sh, long sw, in
  * rounded once to fp32); out float [H][W][3], i.e. a (1,3,H,W) tensor in channels_last memory. */
 int u2pl_infer_input_u8_f32(const unsigned char* img_hwc, int h, int w, const float* lut, float* out_hwc, int H, int W,
                             hipStream_t stream);
+/* Test-time flip / probability fusion (the block eval.py:166-180 leaves commented out): one view's low-resolution logits
+ * in [C][h][w] (through strides) are interpolated (bilinear, align_corners=True: the bits u2pl_bilinear_up_f32 would store)
+ * to the hc x wc window at (h0, w0) of pred [C][H][W]; with flip the window pixel x takes column wc-1-x; with softmax the
+ * C values of a pixel become exp(v - max) / sum (classes upward, ~1 ulp exponential); pred += weight * that; with bump
+ * count [H][W] += 1 inside the window (count may be NULL when bump == 0).  One owner per element, no atomics.
+ * NULL pred / in, NULL count with bump, C outside [1, 256], h or w < 1, a window not inside the accumulator: 1001. */
+int u2pl_window_fuse_f32(float* pred, float* count, int C, int H, int W, const float* in, long sc, long sh, long sw, int h,
+                         int w, int h0, int w0, int hc, int wc, int flip, int softmax, float weight, int bump,
+                         hipStream_t stream);
 
 /* ---- conv.hip (implicit GEMM on v_mfma_f32_32x32x2_f32) -------------------- */
 /* nn.Conv2d forward (NHWC rows, weights [Cout][R][S][Cin]): resnet.py:25-41,178-186;

@@ -2,8 +2,9 @@
 """Inference CLI with the reference's surface (infer.py:27-134): --config --model_path --save_folder; every image of the
 validation list is resized to the input scale (769 x 769 for Cityscapes, 513 x 513 otherwise, or --input_scale H W),
 run through the network once, and its prediction written to <save_folder>/gray/<file name> (class indices) and
-<save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14).  --half (this project's
-option): the forward pass on the fp16 path."""
+<save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14).  This project's options: --half,
+the forward pass on the fp16 path; --flip / --prob, test-time fusion of the image with its mirror image / of
+class probabilities instead of logits."""
 import argparse
 import os
 import sys
@@ -25,12 +26,19 @@ def get_parser():
     return p
 
 
-def get_cli_parser():
-    """get_parser() keeps the reference's surface; the options only this project has are added here"""
+def get_cli_parser(fusion=False):
+    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, and with
+    fusion=True (what main() parses) the test-time fusion options --flip and --prob"""
     p = get_parser()
     p.add_argument("--half", action="store_true", default=False,
                    help="forward pass with fp16 activations and weights (u2pl_amd.half); an image whose pass saturates is "
                         "run again in fp32")
+    if not fusion:
+        return p
+    p.add_argument("--flip", action="store_true", default=False,
+                   help="test-time flip: every image also runs mirrored, the result is mirrored back and the two are averaged")
+    p.add_argument("--prob", action="store_true", default=False,
+                   help="fuse class probabilities (softmax per view) instead of raw logits")
     return p
 
 
@@ -43,7 +51,7 @@ def main():
     from u2pl_amd.engine import load_state
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_cli_parser().parse_args()
+    args = get_cli_parser(fusion=True).parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
@@ -65,7 +73,7 @@ def main():
     for image_path, _ in tqdm(items):
         name = image_path.split("/")[-1]
         img = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
-        label, rgb = I.infer_image(model, img, lut, input_scale, palette, half=half)[:2]
+        label, rgb = I.infer_image(model, img, lut, input_scale, palette, half=half, flip=args.flip, prob=args.prob)[:2]
         Image.fromarray(rgb.cpu().numpy()).save(os.path.join(color, name))
         Image.fromarray(label.cpu().numpy()).save(os.path.join(gray, name))
     if half is not None:

@@ -1,8 +1,10 @@
 // Prediction-side kernels (reference infer.py:118-134, eval.py:294-300):
 //   u2pl_infer_input_u8_f32   decoded uint8 image -> normalised, resized network input (channels_last)
 //   u2pl_predict_map_f32      low-resolution logits -> uint8 label map (+ RGB image through a palette)
-// Both use ac_coord and the three-FMA expression of k_bilinear_up (reliability.hip), in that order, so an interpolated
-// value has the bits u2pl_bilinear_up_f32 would have stored; neither writes a full-resolution float tensor per class.
+//   u2pl_window_fuse_f32      one view's low-resolution logits -> (mirrored) (softmax) += into a window of the accumulator
+// All use ac_coord and the three-FMA expression of k_bilinear_up (reliability.hip), in that order, so an interpolated
+// value has the bits u2pl_bilinear_up_f32 would have stored; none writes a full-resolution float tensor per class besides
+// the accumulator itself.
 #include "common.h"
 #include "u2pl_hip.h"
 
@@ -143,6 +145,127 @@ U2PL_API int u2pl_infer_input_u8_f32(const unsigned char* img_hwc, int h, int w,
     if (total == 0) return 0;
     U2PL_LAUNCH(k_infer_input, dim3(grid_for(total, 256)), dim3(256), 0, stream, img_hwc, h, w, lut, out_hwc, H, W,
                 ac_scale_host(h, H), ac_scale_host(w, W));
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Test-time flip / probability fusion (the block the reference leaves commented out in eval.py:166-180): one view's
+// low-resolution logits are interpolated to the window size, mirrored back when the view was a mirrored image, turned into
+// class probabilities, weighted and added into the window of the accumulator.  A thread owns 4 consecutive window pixels of
+// one row and lanes run along the row, so every class plane is read and written in contiguous runs: 16-byte accesses when the
+// quad is whole and its address allows (w0 and W are arbitrary, and the alignment changes from plane to plane), scalar ones
+// otherwise.  C is a runtime value: instead of keeping v[0..C) per thread (a runtime-indexed array lives in scratch) the
+// classes are swept three times -- maximum, sum of exponentials (classes upward), write -- and the taps recomputed; the
+// low-resolution tensor is L2 resident.  Every output element has one owner and there are no atomics: windows are successive
+// launches on one stream, and two runs give the same bits.  expf is the ~1 ulp library exponential on purpose (the error of
+// the fast intrinsic grows with |v - m|).
+// ---------------------------------------------------------------------------
+template <bool SOFTMAX>
+__global__ void __launch_bounds__(256)
+k_window_fuse(float* __restrict__ pred, float* __restrict__ count, int C, int H, int W, const float* __restrict__ in, long sc,
+              long sh, long sw, int h, int w, int h0, int w0, int hc, int wc, int flip, float weight, int bump, float sy,
+              float sx) {
+    const int Wq = (wc + 3) >> 2;
+    const long total = (long)hc * Wq;
+    const long plane = (long)H * W;
+    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+        const int q = (int)(p % Wq);
+        const int y = (int)(p / Wq);
+        const int x0 = q << 2;
+        const AcCoord cy = ac_coord(y, sy, h);
+        const long r0 = cy.i0 * sh, r1 = cy.i1 * sh;
+        long c0[4], c1[4];
+        float l0[4], l1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = min(x0 + j, wc - 1);   // past the window's edge: recompute its last pixel, store nothing
+            const AcCoord cx = ac_coord(flip ? wc - 1 - x : x, sx, w);
+            c0[j] = cx.i0 * sw;
+            c1[j] = cx.i1 * sw;
+            l0[j] = cx.l0;
+            l1[j] = cx.l1;
+        }
+        auto value = [&](const float* t0, const float* t1, int j) {
+            const float top = __fmaf_rn(l0[j], t0[c0[j]], __fmul_rn(l1[j], t0[c1[j]]));
+            const float bot = __fmaf_rn(l0[j], t1[c0[j]], __fmul_rn(l1[j], t1[c1[j]]));
+            return __fmaf_rn(cy.l0, top, __fmul_rn(cy.l1, bot));
+        };
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+        if (SOFTMAX) {
+            for (int c = 0; c < C; ++c) {
+                const float* t0 = in + c * sc + r0;
+                const float* t1 = in + c * sc + r1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float v = value(t0, t1, j);
+                    m[j] = c == 0 ? v : fmaxf(m[j], v);
+                }
+            }
+            for (int c = 0; c < C; ++c) {
+                const float* t0 = in + c * sc + r0;
+                const float* t1 = in + c * sc + r1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum[j] = __fadd_rn(sum[j], expf(__fsub_rn(value(t0, t1, j), m[j])));
+            }
+        }
+        const long px = (long)(h0 + y) * W + w0 + x0;
+        const bool full = x0 + 4 <= wc;
+        for (int c = 0; c < C; ++c) {
+            const float* t0 = in + c * sc + r0;
+            const float* t1 = in + c * sc + r1;
+            float s[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = value(t0, t1, j);
+                s[j] = __fmul_rn(weight, SOFTMAX ? __fdiv_rn(expf(__fsub_rn(v, m[j])), sum[j]) : v);
+            }
+            float* o = pred + c * plane + px;
+            if (full && ((uintptr_t)o & 15) == 0) {
+                float4 a = *(float4*)o;
+                a.x = __fadd_rn(a.x, s[0]);
+                a.y = __fadd_rn(a.y, s[1]);
+                a.z = __fadd_rn(a.z, s[2]);
+                a.w = __fadd_rn(a.w, s[3]);
+                *(float4*)o = a;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < wc) o[j] = __fadd_rn(o[j], s[j]);
+            }
+        }
+        if (bump) {
+            float* o = count + px;
+            if (full && ((uintptr_t)o & 15) == 0) {
+                float4 a = *(float4*)o;
+                a.x += 1.0f;
+                a.y += 1.0f;
+                a.z += 1.0f;
+                a.w += 1.0f;
+                *(float4*)o = a;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < wc) o[j] += 1.0f;
+            }
+        }
+    }
+}
+
+U2PL_API int u2pl_window_fuse_f32(float* pred, float* count, int C, int H, int W, const float* in, long sc, long sh, long sw,
+                                  int h, int w, int h0, int w0, int hc, int wc, int flip, int softmax, float weight, int bump,
+                                  hipStream_t stream) {
+    if (!pred || !in || (bump && !count) || C < 1 || C > 256 || h < 1 || w < 1) return U2PL_EINVAL;
+    if (h0 < 0 || w0 < 0 || hc < 0 || wc < 0 || h0 > H - hc || w0 > W - wc) return U2PL_EINVAL;
+    const long total = (long)hc * ((wc + 3) >> 2);
+    if (total == 0) return 0;
+    const dim3 grid(grid_for(total, 256, 256 * 32));
+    if (softmax)
+        U2PL_LAUNCH(k_window_fuse<true>, grid, dim3(256), 0, stream, pred, count, C, H, W, in, sc, sh, sw, h, w, h0, w0, hc, wc,
+                    flip, weight, bump, ac_scale_host(h, hc), ac_scale_host(w, wc));
+    else
+        U2PL_LAUNCH(k_window_fuse<false>, grid, dim3(256), 0, stream, pred, count, C, H, W, in, sc, sh, sw, h, w, h0, w0, hc, wc,
+                    flip, weight, bump, ac_scale_host(h, hc), ac_scale_host(w, wc));
     U2PL_LAUNCH_CHECK();
     return 0;
 }

@@ -1,6 +1,8 @@
 """Sliding-window / whole-image evaluation (reference eval.py:158-320) on the HIP forward path.
 
   net_process          eval.py:158-181   model(x)["pred"] -> bilinear(align_corners=True) to the input size
+  fuse_window          eval.py:166-180   (commented out upstream) softmax per view, a mirrored view flipped back, the mean
+                                         over views: one u2pl_window_fuse_f32 launch per view (flip= / prob=)
   scale_crop_process   eval.py:184-224   zero-pad to the crop size, windows at stride ceil(crop * 2/3) (the last
                                          window is pulled back inside the image), sum of window logits / window
                                          count, un-pad, bilinear to the label size
@@ -19,9 +21,10 @@ from ._lib import call
 
 
 @torch.no_grad()
-def net_process(model, image, half=None):
-    """image (1,3,h,w) on the GPU -> logits (1,C,h,w), planar.  half: a u2pl_amd.half.HalfPredictor of `model`: the forward
-    runs on the fp16 path; a pass that saturated (its count is nonzero) is recomputed on the fp32 path."""
+def view_logits(model, image, half=None):
+    """image (1,3,h,w) on the GPU -> one view's low-resolution logits (1,C,h',w'), as the decoder leaves them.  half: a
+    u2pl_amd.half.HalfPredictor of `model`: the forward runs on the fp16 path; a pass that saturated (its count is nonzero)
+    is recomputed on the fp32 path."""
     out = None
     if half is not None:
         out, saturated = half(image)
@@ -29,7 +32,35 @@ def net_process(model, image, half=None):
             out = None
     if out is None:
         out = model(image, need_aux=False, need_rep=False)["pred"]
-    return H.bilinear_up(out, image.shape[2:])
+    return out
+
+
+@torch.no_grad()
+def fuse_window(model, crop, pred, count, origin, half=None, flip=False, prob=False, first=None):
+    """test-time fusion of one window (the block eval.py:166-180 leaves commented out), in place: the window's views --
+    `crop`, and with flip its mirror image, whose result is mirrored back -- are interpolated to the crop's size, turned
+    into class probabilities when prob, and their mean is added into pred at origin; count (None: not kept) gains 1.  One
+    u2pl_window_fuse_f32 launch per view; a view's full-resolution logits are never written.  first: view_logits of
+    `crop` when the caller has them already."""
+    size = crop.shape[2:]
+    weight = 0.5 if flip else 1.0
+    if first is None:
+        first = view_logits(model, crop, half)
+    H.window_fuse(pred, count, first, origin, size, False, prob, weight, count is not None)
+    if flip:
+        H.window_fuse(pred, count, view_logits(model, crop.flip(3), half), origin, size, True, prob, weight, False)
+
+
+@torch.no_grad()
+def net_process(model, image, half=None, flip=False, prob=False):
+    """image (1,3,h,w) on the GPU -> logits (1,C,h,w), planar.  half: see view_logits.  flip / prob: the mean over the
+    image and its mirror image / of class probabilities instead of logits (fuse_window with one window = the image)."""
+    out = view_logits(model, image, half)
+    if not (flip or prob):
+        return H.bilinear_up(out, image.shape[2:])
+    fused = torch.zeros((1, out.shape[1]) + tuple(image.shape[2:]), dtype=torch.float32, device=image.device)
+    fuse_window(model, image, fused, None, (0, 0), half, flip, prob, first=out)
+    return fused
 
 
 def window_grid(new_h, new_w, crop_h, crop_w, stride_rate=2 / 3):
@@ -47,8 +78,8 @@ def window_grid(new_h, new_w, crop_h, crop_w, stride_rate=2 / 3):
 
 
 @torch.no_grad()
-def scale_crop_process(model, image, classes, crop_h, crop_w, h, w, stride_rate=2 / 3, half=None):
-    """image (1,3,H,W) GPU tensor -> logits (classes, h, w)."""
+def scale_crop_process(model, image, classes, crop_h, crop_w, h, w, stride_rate=2 / 3, half=None, flip=False, prob=False):
+    """image (1,3,H,W) GPU tensor -> logits (classes, h, w); with flip / prob every window is fused by fuse_window."""
     ori_h, ori_w = image.shape[2:]
     pad_h, pad_w = max(crop_h - ori_h, 0), max(crop_w - ori_w, 0)
     ph, pw = int(pad_h / 2), int(pad_w / 2)
@@ -61,6 +92,9 @@ def scale_crop_process(model, image, classes, crop_h, crop_w, h, w, stride_rate=
     count = torch.zeros((new_h, new_w), dtype=torch.float32, device=image.device)
     for s_h, s_w in window_grid(new_h, new_w, crop_h, crop_w, stride_rate):
         crop = image[:, :, s_h:s_h + crop_h, s_w:s_w + crop_w].contiguous()
+        if flip or prob:
+            fuse_window(model, crop, pred, count, (s_h, s_w), half, flip, prob)
+            continue
         logits = net_process(model, crop, half).contiguous()
         call("u2pl_window_accumulate_f32", pred, count, classes, new_h, new_w, logits, s_h, s_w, crop_h, crop_w)
     call("u2pl_window_normalize_f32", pred, count, classes, new_h, new_w)
@@ -69,13 +103,16 @@ def scale_crop_process(model, image, classes, crop_h, crop_w, h, w, stride_rate=
 
 
 @torch.no_grad()
-def scale_whole_process(model, image, h, w, half=None):
-    return H.bilinear_up(net_process(model, image, half), (h, w))[0]
+def scale_whole_process(model, image, h, w, half=None, flip=False, prob=False):
+    """with flip / prob: one fused window that covers the scaled image (its count would be 1 everywhere: not kept)"""
+    return H.bilinear_up(net_process(model, image, half, flip, prob), (h, w))[0]
 
 
 @torch.no_grad()
-def predict_image(model, image, classes, base_size, crop, scales=(1.0,), use_crop=True, half=None):
-    """image (1,3,h,w) normalised GPU tensor -> summed logits (classes, h, w) (validate_city's inner loop)."""
+def predict_image(model, image, classes, base_size, crop, scales=(1.0,), use_crop=True, half=None, flip=False, prob=False):
+    """image (1,3,h,w) normalised GPU tensor -> summed logits (classes, h, w) (validate_city's inner loop).  flip / prob:
+    per window, the mean over the window and its mirror image / of class probabilities instead of logits; scales are
+    still summed."""
     h, w = image.shape[2:]
     total = torch.zeros((classes, h, w), dtype=torch.float32, device=image.device)
     for scale in scales:
@@ -87,20 +124,21 @@ def predict_image(model, image, classes, base_size, crop, scales=(1.0,), use_cro
             new_h = round(long_size / float(w) * h)
         scaled = image if (new_h, new_w) == (h, w) else H.bilinear_up(image.contiguous(), (new_h, new_w))
         if use_crop:
-            total += scale_crop_process(model, scaled, classes, crop[0], crop[1], h, w, half=half)
+            total += scale_crop_process(model, scaled, classes, crop[0], crop[1], h, w, half=half, flip=flip, prob=prob)
         else:
-            total += scale_whole_process(model, scaled, h, w, half)
+            total += scale_whole_process(model, scaled, h, w, half, flip, prob)
     return total
 
 
 @torch.no_grad()
 def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=True, ignore=255, on_prediction=None,
-             palette=None, half=None):
+             palette=None, half=None, flip=False, prob=False):
     """samples: iterable of (image (3,h,w) float tensor already mean/std normalised, label (h,w) integer array).
     Returns (mIoU, per-class IoU).  on_prediction(i, uint8 map) receives every argmax map (gray dumps); with a
     palette ((256,3) uint8, array or tensor) it is called as on_prediction(i, gray, color): both maps come from one
     u2pl_predict_map_f32 launch on the summed logits (lowest class index wins a tie) and one uint8 copy each.
-    half: a u2pl_amd.half.HalfPredictor of `model`: every forward call runs on the fp16 path (net_process)."""
+    half: a u2pl_amd.half.HalfPredictor of `model`: every forward call runs on the fp16 path (view_logits).
+    flip / prob: test-time fusion of every window (fuse_window); with flip a window costs two forward passes."""
     model.eval()
     dev = next(model.parameters()).device
     hist = torch.zeros(3 * classes, dtype=torch.int64, device=dev)
@@ -108,7 +146,7 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
         palette = torch.as_tensor(palette).to(dev)
     for i, (image, label) in enumerate(samples):
         image = torch.as_tensor(image, dtype=torch.float32).unsqueeze(0).to(dev)
-        logits = predict_image(model, image, classes, base_size, crop, scales, use_crop, half)
+        logits = predict_image(model, image, classes, base_size, crop, scales, use_crop, half, flip, prob)
         lab = torch.as_tensor(np.asarray(label)).to(dev).long().contiguous().unsqueeze(0)
         h, w = lab.shape[1:]
         call("u2pl_confusion_hist_f32", logits.contiguous(), lab, ignore, 1, classes, h, w, hist)

@@ -83,6 +83,31 @@ def predict_map(logits_low, size, palette=None):
     return label, rgb
 
 
+def window_fuse(pred, count, logits, origin, size, flip=False, softmax=False, weight=1.0, bump=True):
+    """One view of test-time flip / probability fusion, in place: F.interpolate(logits, size, 'bilinear',
+    align_corners=True), mirrored back along the width when flip, softmax over the classes when softmax, times weight,
+    added into pred[:, h0:h0+hc, w0:w0+wc]; with bump, count gains 1 inside that window.  pred: contiguous (C,H,W) or
+    (1,C,H,W) float32; count: contiguous (H,W) float32, or None when bump is off; logits: any strided (C,h,w) or
+    (1,C,h,w) view.  The interpolated logits are never written."""
+    _chk_cuda(pred, count, logits)
+    if logits.dim() == 4:
+        if logits.shape[0] != 1:
+            raise _lib.HipError("window_fuse: one view at a time")
+        logits = logits[0]
+    if pred.dim() == 4 and pred.shape[0] == 1:
+        pred = pred[0]
+    if pred.dim() != 3 or logits.dim() != 3 or pred.shape[0] != logits.shape[0] or not pred.is_contiguous():
+        raise _lib.HipError("window_fuse: expected a contiguous (C,H,W) accumulator and (C,h,w) logits of the same C")
+    C, Hh, Ww = pred.shape
+    if bump and count is None:
+        raise _lib.HipError("window_fuse: bump needs a count map")
+    if count is not None and (tuple(count.shape) != (Hh, Ww) or not count.is_contiguous() or count.dtype != torch.float32):
+        raise _lib.HipError("window_fuse: expected a contiguous (H,W) float32 count map")
+    call("u2pl_window_fuse_f32", _f32c(pred), count, C, Hh, Ww, _f32c(logits), logits.stride(0), logits.stride(1),
+         logits.stride(2), logits.shape[1], logits.shape[2], int(origin[0]), int(origin[1]), int(size[0]), int(size[1]),
+         int(bool(flip)), int(bool(softmax)), float(weight), int(bool(bump)))
+
+
 def infer_input(img_u8_hwc, lut, size):
     """decoded image (h,w,3) uint8 -> network input (1,3,H,W) float32 in channels_last memory: lut[c][byte]
     (infer.normalise_lut) then bilinear(align_corners=True) to `size`, in one kernel."""

@@ -5,7 +5,8 @@
   infer_image     infer.py:118-130   table gather + bilinear to the input scale (one kernel), forward, then bilinear to
                                      the image size + argmax + colour lookup (one kernel): neither the resized float
                                      image on the host nor the full-resolution logits exist; half=: the forward on the
-                                     fp16 path (u2pl_amd.half), redone in fp32 when it saturated
+                                     fp16 path (u2pl_amd.half), redone in fp32 when it saturated; flip= / prob=: the
+                                     views fused at the image size (eval.py:166-180, commented out upstream)
   colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables
 """
 import numpy as np
@@ -43,20 +44,37 @@ def normalise_lut(mean, std):
 
 
 @torch.no_grad()
-def infer_image(model, img_u8, lut, input_scale, palette=None, half=None):
+def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=False, prob=False):
     """img_u8 (h,w,3) uint8, lut (3,256) float32, palette (256,3) uint8 or None: GPU tensors.
     -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits).
     half: a u2pl_amd.half.HalfPredictor of `model` -- the forward pass runs with fp16 activations and weights, and the
     result gains a fourth element, fell_back: True when that pass saturated (a stored activation beyond +-65504) and the
-    image was therefore run again on the fp32 path, whose result is then what is returned."""
+    image was therefore run again on the fp32 path, whose result is then what is returned.
+    flip / prob (test-time fusion, evaluate.fuse_window's rule): the views -- the input and, with flip, its mirror image,
+    whose result is mirrored back -- are fused straight to the image size, as class probabilities when prob, into a
+    (C,h,w) accumulator (one u2pl_window_fuse_f32 launch per view), which predict_map reads at identity size; pred is then
+    that accumulator, and fell_back tells whether any view was run again."""
     h, w = img_u8.shape[:2]
     x = H.infer_input(img_u8, lut, input_scale)
     fell_back = False
-    if half is not None:
-        pred, saturated = half(x)
-        fell_back = saturated > 0
-    if half is None or fell_back:
-        pred = model(x, need_aux=False, need_rep=False)["pred"]
+
+    def forward(x):
+        nonlocal fell_back
+        if half is not None:
+            pred, saturated = half(x)
+            if not saturated > 0:
+                return pred
+            fell_back = True
+        return model(x, need_aux=False, need_rep=False)["pred"]
+
+    pred = forward(x)
+    if flip or prob:
+        fused = torch.zeros((pred.shape[1], h, w), dtype=torch.float32, device=pred.device)
+        weight = 0.5 if flip else 1.0
+        H.window_fuse(fused, None, pred, (0, 0), (h, w), False, prob, weight, False)
+        if flip:
+            H.window_fuse(fused, None, forward(x.flip(3)), (0, 0), (h, w), True, prob, weight, False)
+        pred = fused.unsqueeze(0)
     label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
     out = (label[0], None if rgb is None else rgb[0], pred)
     return out if half is None else out + (fell_back,)
