@@ -12,60 +12,143 @@ __device__ __forceinline__ float4 f4mul(float4 a, float4 b) { return make_float4
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
+// r / rows_per_image (the image of a Dropout2d scale) for a thread whose rows go up by `step`, and now and then by `jump` more: one
+// division when the thread starts, an add and a compare per row after that.  I: the type of a row count within one image (long, or
+// int where the host checked)
+template <class I>
+struct ImageOf {
+    int img; I rem, rpi, qs, ms, qj, mj;
+    __device__ __forceinline__ void init(bool on, long r, long step, long jump, long rows_per_image) {
+        img = 0; rem = 0; qs = 0; ms = 0; qj = 0; mj = 0; rpi = 1;
+        if (on) {
+            rpi = (I)rows_per_image;
+            const long q = r / rows_per_image;
+            img = (int)q; rem = (I)(r - q * rows_per_image);
+            qs = (I)(step / rows_per_image); ms = (I)(step - (step / rows_per_image) * rows_per_image);
+            qj = (I)(jump / rows_per_image); mj = (I)(jump - (jump / rows_per_image) * rows_per_image);
+        }
+    }
+    __device__ __forceinline__ void next() {
+        img += (int)qs; rem += ms;
+        if (rem >= rpi) { rem -= rpi; ++img; }
+    }
+    __device__ __forceinline__ void jump() {
+        img += (int)qj; rem += mj;
+        if (rem >= rpi) { rem -= rpi; ++img; }
+    }
+};
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ldg4(const U2PL_GLOBAL char* p) {      // 16 bytes of global memory (see ldg in common.h)
+    const f32x4 v = *(const U2PL_GLOBAL f32x4*)p;
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ float4 ldg4(const float* p) { return ldg4((const U2PL_GLOBAL char*)p); }
+
 // ---------------------------------------------------------------------------
 // Column reduction skeleton: for rows [seg*Mseg, (seg+1)*Mseg) accumulate two
-// per-channel sums produced by Op::get(row, col4, &v0, &v1).
+// per-channel sums produced by Op::Col::get(row, &v0, &v1).
 //   partial: float [seg][nblk][2][C]   ->   out: double [seg][2][C]
+// Op::col(c4, rg, r0, step) is what thread (row rg of a row group, column c4) keeps across its rows (per-channel operands loaded
+// once); the thread then calls get(first row of the group, its row) for the rows r0, r0 + step, r0 + 2 step, ... in this order.
 // ---------------------------------------------------------------------------
 struct StatOp {  // v0 = x - pivot, v1 = (x - pivot)^2     (BN forward statistics)
     const float* x; long ld; const float* pivot;
-    __device__ __forceinline__ void get(long row, int c4, float4& v0, float4& v1) const {
-        float4 v = *(const float4*)(x + row * ld + c4 * 4);
-        if (pivot) v = f4sub(v, *(const float4*)(pivot + c4 * 4));
-        v0 = v; v1 = f4mul(v, v);
+    static constexpr int kMinWaves = 6;
+    struct Col {
+        const float* xc; long ld; float4 pv; bool shift;
+        __device__ __forceinline__ void get(long, long row, float4& v0, float4& v1) {
+            float4 v = *(const float4*)(xc + row * ld);
+            if (shift) v = f4sub(v, pv);
+            v0 = v; v1 = f4mul(v, v);
+        }
+    };
+    __device__ __forceinline__ Col col(int c4, int, long, long) const {
+        return Col{x + c4 * 4, ld, pivot ? *(const float4*)(pivot + c4 * 4) : f4zero(), pivot != nullptr};
     }
 };
 struct SumOp {  // v0 = x, v1 = 0     (global average pool / bias gradient)
     const float* x; long ld;
-    __device__ __forceinline__ void get(long row, int c4, float4& v0, float4& v1) const {
-        v0 = *(const float4*)(x + row * ld + c4 * 4); v1 = f4zero();
-    }
+    static constexpr int kMinWaves = 6;
+    struct Col {
+        const float* xc; long ld;
+        __device__ __forceinline__ void get(long, long row, float4& v0, float4& v1) { v0 = *(const float4*)(xc + row * ld); v1 = f4zero(); }
+    };
+    __device__ __forceinline__ Col col(int c4, int, long, long) const { return Col{x + c4 * 4, ld}; }
 };
 // the ReLU mask of y = relu((x - mean) * invstd * gamma + beta) recomputed from x: the forward's own expression (k_bn_apply, no
 // contraction), so the same bits and the same mask as [y > 0] -- without reading y (round 6: BatchNorms without a residual)
-__device__ __forceinline__ float4 relu_mask_from_x(float4 g, float4 xv, const float* mean, const float* invstd, const float* gamma,
-                                                   const float* beta, int c) {
-    const float4 mu = *(const float4*)(mean + c), is = *(const float4*)(invstd + c), ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
+__device__ __forceinline__ float4 relu_mask_from_x(float4 g, float4 xv, float4 mu, float4 is, float4 ga, float4 be) {
     g.x = ((xv.x - mu.x) * is.x * ga.x + be.x) > 0.f ? g.x : 0.f;
     g.y = ((xv.y - mu.y) * is.y * ga.y + be.y) > 0.f ? g.y : 0.f;
     g.z = ((xv.z - mu.z) * is.z * ga.z + be.z) > 0.f ? g.z : 0.f;
     g.w = ((xv.w - mu.w) * is.w * ga.w + be.w) > 0.f ? g.w : 0.f;
     return g;
 }
-struct BnBwdOp {  // g = dy*[y>0]*drop ; v0 = g, v1 = g * xhat     (BN backward sums)
+__device__ __forceinline__ float4 relu_mask_from_y(float4 g, float4 yy) {
+    g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
+    g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
+    return g;
+}
+// a wave-uniform global address stated as such (all active lanes hold the same value): the load takes its base from scalar registers
+__device__ __forceinline__ const U2PL_GLOBAL char* uniform_global(const void* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (const U2PL_GLOBAL char*)(((unsigned long long)hi << 32) | lo);
+}
+// g = dy*[y>0]*drop ; v0 = g, v1 = g * xhat     (BN backward sums)
+// MASK 0: no ReLU, 1: the mask from y, 2: the mask from x (gamma, relu_beta: the forward's parameters); DROP: Dropout2d scales.
+// Compile-time forms: the row loop is straight-line code with the per-channel operands in registers.
+// Three loads per row and 32 registers of sums: to stay at 6 waves per SIMD a row's address is the wave-uniform base of its
+// row group plus one 32-bit byte offset per tensor that the thread keeps (its row in the group, its column)
+template <int MASK, bool DROP>
+struct BnBwdOp {
     const float* dy; long lddy; const float* x; long ldx; const float* y; long ldy;
     const float* mean; const float* invstd; const float* drop; long rows_per_image; int C;
-    const float* gamma; const float* relu_beta;         // y == NULL and relu_beta != NULL: the mask from x
-    __device__ __forceinline__ void get(long row, int c4, float4& v0, float4& v1) const {
-        float4 g = *(const float4*)(dy + row * lddy + c4 * 4);
-        float4 xv = *(const float4*)(x + row * ldx + c4 * 4);
-        if (y) {
-            float4 yy = *(const float4*)(y + row * ldy + c4 * 4);
-            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-            g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-        } else if (relu_beta) {
-            g = relu_mask_from_x(g, xv, mean, invstd, gamma, relu_beta, c4 * 4);
+    const float* gamma; const float* relu_beta;
+    static constexpr int kMinWaves = DROP && MASK ? 5 : 6;      // (a mask and the image counter: 8 registers over 80)
+    struct Col {
+        const float* dy; long lddy; const float* x; long ldx; const float* y; long ldy; const float* drop;
+        unsigned og, ox, oy; int c, C;
+        float4 mu, is, ga, be;
+        ImageOf<int> im;       // (bn_bwd_sums_fits: rows_per_image < 2^30)
+        __device__ __forceinline__ void get(long rowg, long, float4& v0, float4& v1) {
+            float4 g = ldg4(uniform_global(dy + rowg * lddy) + og);
+            const float4 xv = ldg4(uniform_global(x + rowg * ldx) + ox);
+            if (MASK == 1) g = relu_mask_from_y(g, ldg4(uniform_global(y + rowg * ldy) + oy));
+            if (MASK == 2) g = relu_mask_from_x(g, xv, mu, is, ga, be);
+            if (DROP) { g = f4mul(g, ldg4(drop + (long)im.img * C + c)); im.next(); }
+            v0 = g; v1 = f4mul(g, f4mul(f4sub(xv, mu), is));
         }
-        if (drop) g = f4mul(g, *(const float4*)(drop + (row / rows_per_image) * C + c4 * 4));
-        float4 xh = f4mul(f4sub(xv, *(const float4*)(mean + c4 * 4)), *(const float4*)(invstd + c4 * 4));
-        v0 = g; v1 = f4mul(g, xh);
+    };
+    __device__ __forceinline__ Col col(int c4, int rg, long r0, long step) const {
+        const int c = c4 * 4;
+        Col k;
+        k.dy = dy; k.lddy = lddy; k.x = x; k.ldx = ldx; k.y = y; k.ldy = ldy; k.drop = drop; k.c = c; k.C = C;
+        k.og = (unsigned)((rg * lddy + c) * 4); k.ox = (unsigned)((rg * ldx + c) * 4); k.oy = (unsigned)((rg * ldy + c) * 4);
+        k.mu = ldg4(mean + c); k.is = ldg4(invstd + c);
+        k.ga = MASK == 2 ? ldg4(gamma + c) : f4zero();
+        k.be = MASK == 2 ? ldg4(relu_beta + c) : f4zero();
+        k.im.init(DROP, r0, step, 0, rows_per_image);
+        return k;
     }
 };
+// what BnBwdOp::Col keeps in 32 bits: byte offsets within a row group (at most 256 rows), row counts within an image
+static bool bn_bwd_sums_fits(long lddy, long ldx, long ldy, const float* drop, long rows_per_image) {
+    const long lim = 1L << 21;
+    return lddy < lim && ldx < lim && ldy < lim && (!drop || (rows_per_image > 0 && rows_per_image < (1L << 30)));
+}
 
 // grid = (row blocks, segments, column slabs of 64 float4): enough blocks in flight to cover HBM latency
 // even when the tensor has few rows (layer3/4: 37636 rows x 1024-2048 channels)
+// (at least 6 waves per SIMD: BnBwdOp's three row streams would otherwise take 128 registers and 4 waves)
+#ifdef U2PL_HBM_MAXW
+#define U2PL_COLREDUCE_KERNEL U2PL_HBM_KERNEL
+#else
+#define U2PL_COLREDUCE_KERNEL __launch_bounds__(256, Op::kMinWaves)
+#endif
 template <class Op>
-__global__ U2PL_HBM_KERNEL void k_colreduce_partial(Op op, long Mseg, int C, float* __restrict__ partial) {
+__global__ U2PL_COLREDUCE_KERNEL void k_colreduce_partial(Op op, long Mseg, int C, float* __restrict__ partial) {
     __shared__ float4 sh0[256], sh1[256];
     const int C4 = C >> 2;
     const int slab0 = blockIdx.z * 64;
@@ -79,23 +162,23 @@ __global__ U2PL_HBM_KERNEL void k_colreduce_partial(Op op, long Mseg, int C, flo
     const int c4 = slab0 + cl;
     float4 a0 = f4zero(), a1 = f4zero();
     if (rg < tr) {
-        // 4 independent row streams per thread: keeps >= 4 x 16 B loads in flight per lane
+        // 4 independent row streams per thread (four ordered sums per column)
         float4 b0 = f4zero(), b1 = f4zero(), c0 = f4zero(), c1 = f4zero(), d0 = f4zero(), d1 = f4zero();
-        long r = rb + rg;
-        for (; r + 3 * (long)tr < re; r += 4 * (long)tr) {
-            float4 v0, v1, w0, w1, x0, x1, y0, y1;
-            op.get(r, c4, v0, v1);
-            op.get(r + tr, c4, w0, w1);
-            op.get(r + 2 * (long)tr, c4, x0, x1);
-            op.get(r + 3 * (long)tr, c4, y0, y1);
-            a0 = f4add(a0, v0); a1 = f4add(a1, v1);
-            b0 = f4add(b0, w0); b1 = f4add(b1, w1);
-            c0 = f4add(c0, x0); c1 = f4add(c1, x1);
-            d0 = f4add(d0, y0); d1 = f4add(d1, y1);
-        }
-        for (; r < re; r += tr) {
+        // g: the first row of the thread's row group, the thread's row is g + rg.  g is the same in all lanes that are active
+        // together: every lane runs the main loop from rb, and a lane that left it one trip before the others has the only rows
+        // that remain for the second loop (rg + 3 tr >= the rows left >= 4 tr + rg' has no solution with rg, rg' < tr)
+        long g = rb;
+        typename Op::Col col = op.col(c4, rg, g + rg, tr);
+        for (; g + rg + 3 * (long)tr < re; g += 4 * (long)tr) {
             float4 v0, v1;
-            op.get(r, c4, v0, v1);
+            col.get(g, g + rg, v0, v1);                                  a0 = f4add(a0, v0); a1 = f4add(a1, v1);
+            col.get(g + tr, g + rg + tr, v0, v1);                        b0 = f4add(b0, v0); b1 = f4add(b1, v1);
+            col.get(g + 2 * (long)tr, g + rg + 2 * (long)tr, v0, v1);    c0 = f4add(c0, v0); c1 = f4add(c1, v1);
+            col.get(g + 3 * (long)tr, g + rg + 3 * (long)tr, v0, v1);    d0 = f4add(d0, v0); d1 = f4add(d1, v1);
+        }
+        for (; g + rg < re; g += tr) {
+            float4 v0, v1;
+            col.get(g, g + rg, v0, v1);
             a0 = f4add(a0, v0); a1 = f4add(a1, v1);
         }
         a0 = f4add(f4add(a0, b0), f4add(c0, d0));
@@ -198,19 +281,30 @@ U2PL_API int u2pl_colsum_f32(const float* x, long ld, long Mseg, int nseg, int C
     SumOp op = {x, ld};
     return run_colreduce(op, Mseg, nseg, C, workspace, sums, stream);
 }
+template <int MASK>
+static int run_bn_bwd_sums(const float* dy, long lddy, const float* x, long ldx, const float* y, long ldy, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, const float* drop, long rows_per_image, long M,
+                           int C, void* workspace, double* sums, hipStream_t stream) {
+    if (!bn_bwd_sums_fits(lddy, ldx, ldy, drop, rows_per_image)) return U2PL_EINVAL;
+    if (drop) {
+        BnBwdOp<MASK, true> op = {dy, lddy, x, ldx, y, ldy, mean, invstd, drop, rows_per_image, C, gamma, beta};
+        return run_colreduce(op, M, 1, C, workspace, sums, stream);
+    }
+    BnBwdOp<MASK, false> op = {dy, lddy, x, ldx, y, ldy, mean, invstd, drop, rows_per_image, C, gamma, beta};
+    return run_colreduce(op, M, 1, C, workspace, sums, stream);
+}
 U2PL_API int u2pl_bn_bwd_sums_f32(const float* dy, long lddy, const float* x, long ldx, const float* y, long ldy,
                                   const float* mean, const float* invstd, const float* drop, long rows_per_image,
                                   long M, int C, void* workspace, double* sums, hipStream_t stream) {
-    BnBwdOp op = {dy, lddy, x, ldx, y, ldy, mean, invstd, drop, rows_per_image, C, nullptr, nullptr};
-    return run_colreduce(op, M, 1, C, workspace, sums, stream);
+    if (y) return run_bn_bwd_sums<1>(dy, lddy, x, ldx, y, ldy, mean, invstd, nullptr, nullptr, drop, rows_per_image, M, C, workspace, sums, stream);
+    return run_bn_bwd_sums<0>(dy, lddy, x, ldx, nullptr, 0, mean, invstd, nullptr, nullptr, drop, rows_per_image, M, C, workspace, sums, stream);
 }
 // the same for y = relu(BN(x)) WITHOUT reading y: the mask is recomputed from x (gamma, beta: the forward's parameters)
 U2PL_API int u2pl_bn_bwd_sums_mx_f32(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* invstd,
                                      const float* gamma, const float* beta, const float* drop, long rows_per_image, long M, int C,
                                      void* workspace, double* sums, hipStream_t stream) {
     if (!gamma || !beta) return U2PL_EINVAL;
-    BnBwdOp op = {dy, lddy, x, ldx, nullptr, 0, mean, invstd, drop, rows_per_image, C, gamma, beta};
-    return run_colreduce(op, M, 1, C, workspace, sums, stream);
+    return run_bn_bwd_sums<2>(dy, lddy, x, ldx, nullptr, 0, mean, invstd, gamma, beta, drop, rows_per_image, M, C, workspace, sums, stream);
 }
 
 // sums (global, already all-reduced over ranks) -> mean, invstd, running stats.
@@ -338,36 +432,99 @@ U2PL_API int u2pl_bn_eval_invstd_multi_f32(const void* jobs_dev, int njobs, long
     return 0;
 }
 
+// ---- BatchNorm apply / backward apply: a thread owns one float4 column ------------------------------------------------------
+// A 256-thread block covers tc = min(256, C/4 - slab0) float4 columns (blockIdx.y: slabs of 256 columns) x tr = 256 / tc rows;
+// threads beyond tr x tc are idle (C/4 = 12: 252 of 256 work).  A thread loads or computes its per-channel terms once, then
+// walks chunks of BN_ROWS x tr rows (chunk blockIdx.x, then every gridDim.x-th): its BN_ROWS rows of a chunk, tr apart, are
+// independent loads in flight, and a block reads and writes BN_ROWS x 4 KB of contiguous memory per tensor and chunk, so the
+// grid sweeps each tensor front to back.  The row loop holds no division and no per-channel load.  The grid is at most one
+// resident set of blocks.
+#define BN_ROWS 4
+#ifdef U2PL_HBM_MAXW
+#define U2PL_BN_KERNEL(w) U2PL_HBM_KERNEL
+#else
+#define U2PL_BN_KERNEL(w) __launch_bounds__(256, w)
+#endif
+struct ColOwner { int c; bool active; long r, step, chunk; };   // first channel, has rows, first row, rows between two rows of a chunk, between chunks
+__device__ __forceinline__ ColOwner col_owner(int C) {
+    const int C4 = C >> 2, slab0 = blockIdx.y * 256;
+    const int tc = min(256, C4 - slab0), tr = 256 / tc;
+    const int cl = threadIdx.x % tc, rg = threadIdx.x / tc;
+    ColOwner o;
+    o.c = (slab0 + cl) * 4; o.active = rg < tr;
+    o.step = tr; o.chunk = (long)gridDim.x * BN_ROWS * tr;
+    o.r = (long)blockIdx.x * BN_ROWS * tr + rg;
+    return o;
+}
+static dim3 bn_grid(long M, int C, int blocks_per_cu) {       // blocks_per_cu: the kernel's waves per SIMD (its launch bounds)
+    const int C4 = C / 4, nslab = cdiv(C4, 256), tr = 256 / (C4 < 256 ? C4 : 256);
+    const int cap = 256 * blocks_per_cu / nslab;
+    return dim3(grid_for(M, BN_ROWS * tr, cap > 0 ? cap : 1), nslab);
+}
+
 // y = [relu]( (x - mean)*invstd*gamma + beta [+ res] ) [* drop[n][c]]
-__global__ U2PL_HBM_KERNEL void k_bn_apply(const float* __restrict__ x, long ldx, const float* __restrict__ mean,
+template <int NR>   // NR rows of one column: xp, rp, yp point at the first, sx, sr, sy floats lie between two of them
+__device__ __forceinline__ unsigned bn_apply_rows(const float* xp, long sx, const float* rp, long sr, float* yp, long sy,
+                                                  const float* dropc, int C, ImageOf<long>& im, int relu, float4 mu, float4 is, float4 ga,
+                                                  float4 be, unsigned am) {
+    float4 v[NR], a[NR];
+#pragma unroll
+    for (int u = 0; u < NR; ++u) v[u] = *(const float4*)(xp + u * sx);
+    if (rp) {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) a[u] = *(const float4*)(rp + u * sr);
+    }
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        float4 t = v[u];
+        t.x = (t.x - mu.x) * is.x * ga.x + be.x; t.y = (t.y - mu.y) * is.y * ga.y + be.y;
+        t.z = (t.z - mu.z) * is.z * ga.z + be.z; t.w = (t.w - mu.w) * is.w * ga.w + be.w;
+        if (rp) t = f4add(t, a[u]);
+        if (relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+        if (dropc) { t = f4mul(t, *(const float4*)(dropc + (long)im.img * C)); im.next(); }     // (a cached line)
+        *(float4*)(yp + u * sy) = t;
+        am = amax_bits4(am, t);
+    }
+    return am;
+}
+__global__ U2PL_BN_KERNEL(6) void k_bn_apply(const float* __restrict__ x, long ldx, const float* __restrict__ mean,
                            const float* __restrict__ invstd, const float* __restrict__ gamma,
                            const float* __restrict__ beta, const float* __restrict__ res, long ldr, int relu,
                            const float* __restrict__ drop, long rows_per_image, float* __restrict__ y, long ldy,
                            long M, int C, unsigned* __restrict__ y_amax) {
-    const int C4 = C >> 2;
-    const long total = M * C4;
+    const ColOwner o = col_owner(C);
     unsigned am = 0u;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / C4;
-        const int c = (int)(i % C4) * 4;
-        float4 v = *(const float4*)(x + r * ldx + c);
+    if (o.active) {
+        const int c = o.c;
         const float4 mu = *(const float4*)(mean + c), is = *(const float4*)(invstd + c);
         const float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-        v.x = (v.x - mu.x) * is.x * ga.x + be.x; v.y = (v.y - mu.y) * is.y * ga.y + be.y;
-        v.z = (v.z - mu.z) * is.z * ga.z + be.z; v.w = (v.w - mu.w) * is.w * ga.w + be.w;
-        if (res) v = f4add(v, *(const float4*)(res + r * ldr + c));
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        if (drop) v = f4mul(v, *(const float4*)(drop + (r / rows_per_image) * C + c));
-        *(float4*)(y + r * ldy + c) = v;
-        am = amax_bits4(am, v);
+        ImageOf<long> im;
+        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);
+        const float* dropc = drop ? drop + c : nullptr;
+        const long sx = o.step * ldx, sr = o.step * ldr, sy = o.step * ldy;      // (row bases stay 64-bit: tensors beyond 2^31 bytes)
+        const float* xp = x + o.r * ldx + c;
+        const float* rp = res ? res + o.r * ldr + c : nullptr;
+        float* yp = y + o.r * ldy + c;
+        for (long r = o.r; r < M; r += o.chunk) {
+            if (r + (BN_ROWS - 1) * o.step < M) {
+                am = bn_apply_rows<BN_ROWS>(xp, sx, rp, sr, yp, sy, dropc, C, im, relu, mu, is, ga, be, am);
+            } else {      // the last chunk of the tensor
+                for (int u = 0; r + u * o.step < M; ++u)
+                    am = bn_apply_rows<1>(xp + u * sx, sx, rp ? rp + u * sr : nullptr, sr, yp + u * sy, sy, dropc, C, im, relu, mu, is,
+                                          ga, be, am);
+            }
+            im.jump();
+            xp += o.chunk * ldx; yp += o.chunk * ldy;
+            if (rp) rp += o.chunk * ldr;
+        }
     }
-    if (y_amax) amax_wave_publish(am, y_amax);       // (uniform branch; split-fp16: the output is a GEMM operand)
+    if (y_amax) amax_wave_publish(am, y_amax);       // (uniform branch, every lane; split-fp16: the output is a GEMM operand)
 }
 U2PL_API int u2pl_bn_apply_f32(const float* x, long ldx, const float* mean, const float* invstd, const float* gamma,
                                const float* beta, const float* res, long ldr, int relu, const float* drop,
                                long rows_per_image, float* y, long ldy, long M, int C, hipStream_t stream) {
     if (C % 4) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_bn_apply, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
+    U2PL_LAUNCH(k_bn_apply, bn_grid(M, C, 6), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
                        beta, res, ldr, relu, drop, rows_per_image, y, ldy, M, C, (unsigned*)nullptr);
     U2PL_LAUNCH_CHECK();
     return 0;
@@ -377,7 +534,7 @@ U2PL_API int u2pl_bn_apply_amax_f32(const float* x, long ldx, const float* mean,
                                     const float* beta, const float* res, long ldr, int relu, const float* drop,
                                     long rows_per_image, float* y, long ldy, long M, int C, float* y_amax, hipStream_t stream) {
     if (C % 4) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_bn_apply, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
+    U2PL_LAUNCH(k_bn_apply, bn_grid(M, C, 6), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
                        beta, res, ldr, relu, drop, rows_per_image, y, ldy, M, C, (unsigned*)y_amax);
     U2PL_LAUNCH_CHECK();
     return 0;
@@ -385,7 +542,44 @@ U2PL_API int u2pl_bn_apply_amax_f32(const float* x, long ldx, const float* mean,
 
 // g = dy*[y>0]*drop ; dres = g ; dx = gamma*invstd*(g - S0/cnt - xhat*S1/cnt)  (train)
 //                                dx = gamma*invstd*g                           (eval: sums == NULL)
-__global__ U2PL_HBM_KERNEL void k_bn_bwd_apply(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
+struct BnBwdCol { float4 mu, is, ga, be, gi, m0, m1; };      // a column's terms: gi = gamma*invstd, m0 = S0/cnt, m1 = S1/cnt
+template <int NR>   // NR rows of one column (pointers at the first row, s* floats between two rows); mode bits: 1 train, 2 mask from x
+__device__ __forceinline__ void bn_bwd_rows(const float* gp, long sg, const float* xp, long sx, const float* yp, long sy, float* dxp,
+                                            long sdx, float* drp, long sdr, const float* dropc, int C, ImageOf<long>& im, int mode,
+                                            const BnBwdCol& k, unsigned& am_x, unsigned& am_r) {
+    float4 g[NR], xv[NR], yy[NR];
+#pragma unroll
+    for (int u = 0; u < NR; ++u) g[u] = *(const float4*)(gp + u * sg);
+    if (yp) {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) yy[u] = *(const float4*)(yp + u * sy);
+    }
+    if (mode) {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) xv[u] = *(const float4*)(xp + u * sx);
+    }
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        float4 t = g[u];
+        if (yp) t = relu_mask_from_y(t, yy[u]);
+        else if (mode & 2) t = relu_mask_from_x(t, xv[u], k.mu, k.is, k.ga, k.be);   // (y = relu(BN(x)) without a residual)
+        if (dropc) { t = f4mul(t, *(const float4*)(dropc + (long)im.img * C)); im.next(); }     // (a cached line)
+        if (drp) *(float4*)(drp + u * sdr) = t;
+        am_r = amax_bits4(am_r, t);
+        float4 o;
+        if (mode & 1) {
+            o.x = k.gi.x * (t.x - k.m0.x - (xv[u].x - k.mu.x) * k.is.x * k.m1.x);
+            o.y = k.gi.y * (t.y - k.m0.y - (xv[u].y - k.mu.y) * k.is.y * k.m1.y);
+            o.z = k.gi.z * (t.z - k.m0.z - (xv[u].z - k.mu.z) * k.is.z * k.m1.z);
+            o.w = k.gi.w * (t.w - k.m0.w - (xv[u].w - k.mu.w) * k.is.w * k.m1.w);
+        } else {
+            o = f4mul(k.gi, t);
+        }
+        *(float4*)(dxp + u * sdx) = o;
+        am_x = amax_bits4(am_x, o);
+    }
+}
+__global__ U2PL_BN_KERNEL(4) void k_bn_bwd_apply(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
                                const float* __restrict__ y, long ldy, const float* __restrict__ mean,
                                const float* __restrict__ invstd, const float* __restrict__ gamma,
                                const float* __restrict__ drop, long rows_per_image,
@@ -394,45 +588,50 @@ __global__ U2PL_HBM_KERNEL void k_bn_bwd_apply(const float* __restrict__ dy, lon
                                float* __restrict__ gsink, float* __restrict__ bsink, int accumulate,
                                unsigned* __restrict__ dx_amax, unsigned* __restrict__ dres_amax, const float* __restrict__ relu_beta) {
     unsigned am_x = 0u, am_r = 0u;
-    if (psums) {   // (u2pl_bn_bwd_apply_pg_f32) the parameter gradients ride along: k_sums_to_f32's arithmetic, dgamma = S1, dbeta = S0
+    if (psums && blockIdx.y == 0) {   // (u2pl_bn_bwd_apply_pg_f32) the parameter gradients ride along: k_sums_to_f32's arithmetic, dgamma = S1, dbeta = S0
         for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < C; i += (long)gridDim.x * blockDim.x) {
             gsink[i] = (accumulate ? gsink[i] : 0.f) + (float)(psums[C + i] * (double)1.0f);
             bsink[i] = (accumulate ? bsink[i] : 0.f) + (float)(psums[i] * (double)1.0f);
         }
     }
-    const int C4 = C >> 2;
-    const long total = M * C4;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / C4;
-        const int c = (int)(i % C4) * 4;
-        float4 g = *(const float4*)(dy + r * lddy + c);
-        if (y) {
-            const float4 yy = *(const float4*)(y + r * ldy + c);
-            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-            g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
-        } else if (relu_beta) {       // (y = relu(BN(x)) without a residual: the mask from x, see relu_mask_from_x)
-            g = relu_mask_from_x(g, *(const float4*)(x + r * ldx + c), mean, invstd, gamma, relu_beta, c);
-        }
-        if (drop) g = f4mul(g, *(const float4*)(drop + (r / rows_per_image) * C + c));
-        if (dres) *(float4*)(dres + r * lddr + c) = g;
-        am_r = amax_bits4(am_r, g);
-        const float4 is = *(const float4*)(invstd + c), ga = *(const float4*)(gamma + c);
-        float4 o;
+    const ColOwner o = col_owner(C);
+    if (o.active) {
+        const int c = o.c;
+        const int mode = (sums ? 1 : 0) | (!y && relu_beta ? 2 : 0);
+        BnBwdCol k;
+        k.is = *(const float4*)(invstd + c); k.ga = *(const float4*)(gamma + c);
+        k.gi = f4mul(k.ga, k.is);
+        k.mu = mode ? *(const float4*)(mean + c) : f4zero();
+        k.be = (mode & 2) ? *(const float4*)(relu_beta + c) : f4zero();
+        k.m0 = f4zero(); k.m1 = f4zero();
         if (sums) {
-            const float4 xv = *(const float4*)(x + r * ldx + c), mu = *(const float4*)(mean + c);
-            const float m0x = (float)(sums[c] / count), m0y = (float)(sums[c + 1] / count);
-            const float m0z = (float)(sums[c + 2] / count), m0w = (float)(sums[c + 3] / count);
-            const float m1x = (float)(sums[C + c] / count), m1y = (float)(sums[C + c + 1] / count);
-            const float m1z = (float)(sums[C + c + 2] / count), m1w = (float)(sums[C + c + 3] / count);
-            o.x = ga.x * is.x * (g.x - m0x - (xv.x - mu.x) * is.x * m1x);
-            o.y = ga.y * is.y * (g.y - m0y - (xv.y - mu.y) * is.y * m1y);
-            o.z = ga.z * is.z * (g.z - m0z - (xv.z - mu.z) * is.z * m1z);
-            o.w = ga.w * is.w * (g.w - m0w - (xv.w - mu.w) * is.w * m1w);
-        } else {
-            o = f4mul(f4mul(ga, is), g);
+            k.m0 = make_float4((float)(sums[c] / count), (float)(sums[c + 1] / count), (float)(sums[c + 2] / count),
+                               (float)(sums[c + 3] / count));
+            k.m1 = make_float4((float)(sums[C + c] / count), (float)(sums[C + c + 1] / count), (float)(sums[C + c + 2] / count),
+                               (float)(sums[C + c + 3] / count));
         }
-        *(float4*)(dx + r * lddx + c) = o;
-        am_x = amax_bits4(am_x, o);
+        ImageOf<long> im;
+        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);
+        const float* dropc = drop ? drop + c : nullptr;
+        const long sg = o.step * lddy, sx = o.step * ldx, sy = o.step * ldy, sdx = o.step * lddx, sdr = o.step * lddr;
+        const float* gp = dy + o.r * lddy + c;
+        const float* xp = x + o.r * ldx + c;
+        const float* yp = y ? y + o.r * ldy + c : nullptr;
+        float* dxp = dx + o.r * lddx + c;
+        float* drp = dres ? dres + o.r * lddr + c : nullptr;
+        for (long r = o.r; r < M; r += o.chunk) {
+            if (r + (BN_ROWS - 1) * o.step < M) {
+                bn_bwd_rows<BN_ROWS>(gp, sg, xp, sx, yp, sy, dxp, sdx, drp, sdr, dropc, C, im, mode, k, am_x, am_r);
+            } else {      // the last chunk of the tensor
+                for (int u = 0; r + u * o.step < M; ++u)
+                    bn_bwd_rows<1>(gp + u * sg, sg, xp + u * sx, sx, yp ? yp + u * sy : nullptr, sy, dxp + u * sdx, sdx,
+                                   drp ? drp + u * sdr : nullptr, sdr, dropc, C, im, mode, k, am_x, am_r);
+            }
+            im.jump();
+            gp += o.chunk * lddy; xp += o.chunk * ldx; dxp += o.chunk * lddx;
+            if (yp) yp += o.chunk * ldy;
+            if (drp) drp += o.chunk * lddr;
+        }
     }
     if (dx_amax) amax_wave_publish(am_x, dx_amax);
     if (dres_amax) amax_wave_publish(am_r, dres_amax);
@@ -442,7 +641,7 @@ U2PL_API int u2pl_bn_bwd_apply_f32(const float* dy, long lddy, const float* x, l
                                    long rows_per_image, const double* sums, double count, float* dx, long lddx,
                                    float* dres, long lddr, long M, int C, hipStream_t stream) {
     if (C % 4) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_bn_bwd_apply, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
+    U2PL_LAUNCH(k_bn_bwd_apply, bn_grid(M, C, 4), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
                        mean, invstd, gamma, drop, rows_per_image, sums, count, dx, lddx, dres, lddr, M, C, (const double*)nullptr,
                        (float*)nullptr, (float*)nullptr, 0, (unsigned*)nullptr, (unsigned*)nullptr, (const float*)nullptr);
     U2PL_LAUNCH_CHECK();
@@ -456,7 +655,7 @@ U2PL_API int u2pl_bn_bwd_apply_pg_f32(const float* dy, long lddy, const float* x
                                       float* dres, long lddr, long M, int C, const double* psums, float* gsink, float* bsink,
                                       int accumulate, hipStream_t stream) {
     if (C % 4 || !psums || !gsink || !bsink) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_bn_bwd_apply, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
+    U2PL_LAUNCH(k_bn_bwd_apply, bn_grid(M, C, 4), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
                        mean, invstd, gamma, drop, rows_per_image, sums, count, dx, lddx, dres, lddr, M, C, psums, gsink, bsink,
                        accumulate, (unsigned*)nullptr, (unsigned*)nullptr, (const float*)nullptr);
     U2PL_LAUNCH_CHECK();
@@ -470,7 +669,7 @@ U2PL_API int u2pl_bn_bwd_apply_amax_f32(const float* dy, long lddy, const float*
                                         float* dres, long lddr, long M, int C, const double* psums, float* gsink, float* bsink,
                                         int accumulate, float* dx_amax, float* dres_amax, const float* relu_beta, hipStream_t stream) {
     if (C % 4 || (psums && (!gsink || !bsink)) || (relu_beta && y)) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_bn_bwd_apply, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
+    U2PL_LAUNCH(k_bn_bwd_apply, bn_grid(M, C, 4), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
                        mean, invstd, gamma, drop, rows_per_image, sums, count, dx, lddx, dres, lddr, M, C, psums, gsink, bsink,
                        accumulate, (unsigned*)dx_amax, (unsigned*)dres_amax, relu_beta);
     U2PL_LAUNCH_CHECK();
