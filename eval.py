@@ -3,7 +3,10 @@
 --save_folder --crop; Cityscapes lists -> sliding-window evaluation, VOC lists -> whole-image evaluation.  Every
 prediction is written to <save_folder>/gray/<name>.png and, in the dataset's colours, <save_folder>/color/<name>.png.
 This project's options: --half, the forward passes on the fp16 path; --flip / --prob, test-time fusion of every
-window (a mirrored view, class probabilities instead of logits) -- with --scales this is "ms+flip"."""
+window (a mirrored view, class probabilities instead of logits; DESIGN 3.10) -- with --scales this is "ms+flip";
+--entropy, the softmax entropy of the summed scores as an 8-bit heat map in <save_folder>/entropy/<name>.png; --drop_percent P,
+gray/ and color/ keep the P per cent lowest-entropy pixels of each image (the rest 255) and the mIoU on the reliable and on the
+unreliable pixels is printed next to the usual one."""
 import argparse
 import os
 import sys
@@ -27,9 +30,10 @@ def get_parser():
     return p
 
 
-def get_cli_parser(fusion=False):
-    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, and with
-    fusion=True (what main() parses) the test-time fusion options --flip and --prob"""
+def get_cli_parser(fusion=False, reliability=False):
+    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, with
+    fusion=True the test-time fusion options --flip and --prob, and with reliability=True as well (what main() parses)
+    --drop_percent and --entropy"""
     p = get_parser()
     p.add_argument("--half", action="store_true", default=False,
                    help="forward passes with fp16 activations and weights (u2pl_amd.half); a pass that saturates is "
@@ -40,6 +44,12 @@ def get_cli_parser(fusion=False):
                    help="test-time flip: every window also runs mirrored, the result is mirrored back and the two are averaged")
     p.add_argument("--prob", action="store_true", default=False,
                    help="fuse class probabilities (softmax per view) instead of raw logits, per window and scale")
+    if reliability:
+        p.add_argument("--drop_percent", type=float, default=None, metavar="P",
+                       help="keep the P per cent lowest-entropy pixels of every image, write 255 for the rest, and report "
+                            "the mIoU on reliable and unreliable pixels (trainer.unsupervised.drop_percent's meaning)")
+        p.add_argument("--entropy", action="store_true", default=False,
+                       help="write the per-pixel softmax entropy as an 8-bit heat map to <save_folder>/entropy/<name>.png")
     return p
 
 
@@ -66,7 +76,7 @@ def main():
     from u2pl_amd.infer import colormap
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_cli_parser(fusion=True).parse_args()
+    args = get_cli_parser(fusion=True, reliability=True).parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     mean, std = np.asarray(ds["mean"], np.float32), np.asarray(ds["std"], np.float32)
@@ -91,19 +101,34 @@ def main():
             img = (np.asarray(Image.open(ip).convert("RGB")).astype(np.float32) - mean) / std
             yield torch.from_numpy(img).permute(2, 0, 1).contiguous(), np.asarray(Image.open(lp).convert("L")).astype(np.uint8)
 
-    def dump(i, pred, rgb):
+    if not 0.0 <= (100.0 if args.drop_percent is None else args.drop_percent) <= 100.0:
+        raise SystemExit("--drop_percent is a percentile in [0, 100]")
+    heat_dir = os.path.join(args.save_folder, "entropy")
+    if args.entropy:
+        os.makedirs(heat_dir, exist_ok=True)
+
+    def dump(i, pred, rgb, heat=None):
         name = os.path.basename(items[i][0]).split(".")[0] + ".png"
         Image.fromarray(pred).save(os.path.join(gray, name))
         Image.fromarray(rgb).save(os.path.join(color, name))
+        if heat is not None:
+            Image.fromarray(heat).save(os.path.join(heat_dir, name))
 
     city = "cityscapes" in ds["type"]
-    miou, iou = E.evaluate(model, samples(), classes, args.base_size, crop, args.scales, use_crop=city or args.crop,
-                           ignore=ds.get("ignore_label", 255), on_prediction=dump,
-                           palette=colormap("cityscapes" if city else "pascal"), half=half, flip=args.flip,
-                           prob=args.prob)
+    kw = {}
+    if args.drop_percent is not None or args.entropy:
+        kw = dict(drop_percent=args.drop_percent, entropy=args.entropy)
+    miou, iou, *rel = E.evaluate(model, samples(), classes, args.base_size, crop, args.scales, use_crop=city or args.crop,
+                                 ignore=ds.get("ignore_label", 255), on_prediction=dump,
+                                 palette=colormap("cityscapes" if city else "pascal"), half=half, flip=args.flip,
+                                 prob=args.prob, **kw)
     for c, v in enumerate(iou):
         print(f" * class [{c}] IoU {v * 100:.2f}")
     print(f" * mIoU {miou * 100:.2f}")
+    if rel:
+        print(f" * mIoU reliable ({args.drop_percent:g}) {rel[0]['miou_reliable'] * 100:.2f}")
+        print(f" * mIoU unreliable {rel[0]['miou_unreliable'] * 100:.2f}")
+        print(f" * coverage {rel[0]['coverage'] * 100:.2f}")
     if half is not None:
         print(half.log_line())
 

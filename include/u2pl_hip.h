@@ -195,6 +195,26 @@ int u2pl_infer_input_u8_f32(const unsigned char* img_hwc, int h, int w, const fl
 int u2pl_window_fuse_f32(float* pred, float* count, int C, int H, int W, const float* in, long sc, long sh, long sw, int h,
                          int w, int h0, int w0, int hc, int wc, int flip, int softmax, float weight, int bump,
                          hipStream_t stream);
+/* Reliability maps on the prediction side: label and softmax entropy of every pixel from the low-resolution scores
+ * [N][C][h][w] (through strides) in one launch; the full-resolution scores are never written (identity size h == H, w == W
+ * is what the fused accumulators use).  label uint8 [N][H][W]: the bits u2pl_predict_map_f32 stores (infer.py:127-130, lowest
+ * index wins a tie).  entropy float [N][H][W]: prob == 0, scores are logits: -sum(p * log(p)) of their softmax as
+ * logf(s) - t / s (loss_helper.py:35-36, train_semi.py:402-403), the bits u2pl_entropy_up_f32 stores with label == NULL;
+ * prob == 1, scores are non-negative class weights a_c (sums of softmaxes): p_c = a_c / S with S = sum a_c (classes upward),
+ * -sum(p_c * logf(p_c)) over p_c > 0, and logf(C) where S <= 0; never NaN for finite input.
+ * Does not touch a select workspace: run u2pl_select_f32 with hist0_done = 0 and ws[0] = ws[1] = N*H*W.
+ * C outside [1, 256], a NULL pointer, h, w, H or W < 1: 1001. */
+int u2pl_predict_entropy_f32(const float* in, long sn, long sc, long sh, long sw, int N, int C, int h, int w, int H, int W,
+                             int prob, unsigned char* label, float* entropy, hipStream_t stream);
+/* The drop rule of loss_helper.py:41-43 on uint8 maps, in place over n pixels: where thr_bits != NULL and
+ * entropy[p] >= *thr_bits (float bits in device memory, e.g. a threshold word of the select workspace) label[p] = 255, and
+ * *ndropped (may be NULL) gains the number of such pixels (integer atomics, one per block: deterministic).  Then, read after
+ * the drop, rgb[p] = palette[label[p]] (palette uint8 [256][3], rgb uint8 [n][3]; both NULL: no colours) and, when
+ * heat != NULL, heat[p] = clamp((int)(entropy[p] * heat_scale + 0.5f), 0, 255) with the product and the sum each rounded to
+ * fp32.  NULL label / entropy, exactly one of palette / rgb NULL: 1001. */
+int u2pl_reliable_map_u8(unsigned char* label, const float* entropy, const unsigned* thr_bits, long n,
+                         const unsigned char* palette, unsigned char* rgb, unsigned char* heat, float heat_scale,
+                         unsigned* ndropped, hipStream_t stream);
 
 /* ---- conv.hip (implicit GEMM on v_mfma_f32_32x32x2_f32) -------------------- */
 /* nn.Conv2d forward (NHWC rows, weights [Cout][R][S][Cin]): resnet.py:25-41,178-186;

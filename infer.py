@@ -4,7 +4,9 @@ validation list is resized to the input scale (769 x 769 for Cityscapes, 513 x 5
 run through the network once, and its prediction written to <save_folder>/gray/<file name> (class indices) and
 <save_folder>/color/<file name> (Pascal colours for every dataset, as upstream: DESIGN Q14).  This project's options: --half,
 the forward pass on the fp16 path; --flip / --prob, test-time fusion of the image with its mirror image / of
-class probabilities instead of logits."""
+class probabilities instead of logits; --entropy, the softmax entropy of every pixel as an 8-bit heat map in
+<save_folder>/entropy/<stem>.png (255 = log C); --drop_percent P, gray/ and color/ hold the labels as the method's own
+pseudo-label rule would keep them: the P per cent lowest-entropy pixels of each image, the rest 255."""
 import argparse
 import os
 import sys
@@ -26,9 +28,10 @@ def get_parser():
     return p
 
 
-def get_cli_parser(fusion=False):
-    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, and with
-    fusion=True (what main() parses) the test-time fusion options --flip and --prob"""
+def get_cli_parser(fusion=False, reliability=False):
+    """get_parser() keeps the reference's surface; the options only this project has are added here: --half, with
+    fusion=True the test-time fusion options --flip and --prob, and with reliability=True as well (what main() parses)
+    --drop_percent and --entropy"""
     p = get_parser()
     p.add_argument("--half", action="store_true", default=False,
                    help="forward pass with fp16 activations and weights (u2pl_amd.half); an image whose pass saturates is "
@@ -39,6 +42,12 @@ def get_cli_parser(fusion=False):
                    help="test-time flip: every image also runs mirrored, the result is mirrored back and the two are averaged")
     p.add_argument("--prob", action="store_true", default=False,
                    help="fuse class probabilities (softmax per view) instead of raw logits")
+    if reliability:
+        p.add_argument("--drop_percent", type=float, default=None, metavar="P",
+                       help="keep the P per cent lowest-entropy pixels of every image, write 255 for the rest "
+                            "(trainer.unsupervised.drop_percent's meaning; P in [0, 100])")
+        p.add_argument("--entropy", action="store_true", default=False,
+                       help="write the per-pixel softmax entropy as an 8-bit heat map to <save_folder>/entropy/<stem>.png")
     return p
 
 
@@ -51,7 +60,7 @@ def main():
     from u2pl_amd.engine import load_state
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_cli_parser(fusion=True).parse_args()
+    args = get_cli_parser(fusion=True, reliability=True).parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
@@ -70,12 +79,29 @@ def main():
     if args.half:
         from u2pl_amd.half import HalfPredictor
         half = HalfPredictor(model)
+    reliability = args.drop_percent is not None or args.entropy
+    if not 0.0 <= (100.0 if args.drop_percent is None else args.drop_percent) <= 100.0:
+        raise SystemExit("--drop_percent is a percentile in [0, 100]")
+    heat_dir = os.path.join(args.save_folder, "entropy")
+    if args.entropy:
+        os.makedirs(heat_dir, exist_ok=True)
+    dropped = []       # (ndropped device tensor, pixels) per image: read once, after the loop
     for image_path, _ in tqdm(items):
         name = image_path.split("/")[-1]
         img = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
-        label, rgb = I.infer_image(model, img, lut, input_scale, palette, half=half, flip=args.flip, prob=args.prob)[:2]
+        kw = dict(drop_percent=args.drop_percent, entropy=args.entropy) if reliability else {}
+        out = I.infer_image(model, img, lut, input_scale, palette, half=half, flip=args.flip, prob=args.prob, **kw)
+        label, rgb = out[:2]
         Image.fromarray(rgb.cpu().numpy()).save(os.path.join(color, name))
         Image.fromarray(label.cpu().numpy()).save(os.path.join(gray, name))
+        if args.entropy:
+            Image.fromarray(out[-1]["heat"].cpu().numpy()).save(os.path.join(heat_dir, os.path.splitext(name)[0] + ".png"))
+        if args.drop_percent is not None:
+            dropped.append((out[-1]["ndropped"], label.numel()))
+    if dropped:
+        counts = torch.cat([d for d, _ in dropped]).cpu().numpy()
+        share = float(np.mean(counts / np.array([n for _, n in dropped], dtype=np.float64)))
+        print(f" * dropped pixels (drop_percent {args.drop_percent:g}): mean share {share * 100:.2f} % over {len(dropped)} images")
     if half is not None:
         print(half.log_line())
 

@@ -130,18 +130,34 @@ def predict_image(model, image, classes, base_size, crop, scales=(1.0,), use_cro
     return total
 
 
+def _iou(hist3c):
+    """(3, C) intersection / output / target counts -> (mIoU, per-class IoU), eval.py:302-305"""
+    hh = np.asarray(hist3c, dtype=np.float64)
+    iou = hh[0] / (hh[1] + hh[2] - hh[0] + 1e-10)
+    return float(np.mean(iou)), iou
+
+
 @torch.no_grad()
 def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=True, ignore=255, on_prediction=None,
-             palette=None, half=None, flip=False, prob=False):
+             palette=None, half=None, flip=False, prob=False, drop_percent=None, entropy=False):
     """samples: iterable of (image (3,h,w) float tensor already mean/std normalised, label (h,w) integer array).
     Returns (mIoU, per-class IoU).  on_prediction(i, uint8 map) receives every argmax map (gray dumps); with a
     palette ((256,3) uint8, array or tensor) it is called as on_prediction(i, gray, color): both maps come from one
     u2pl_predict_map_f32 launch on the summed logits (lowest class index wins a tie) and one uint8 copy each.
     half: a u2pl_amd.half.HalfPredictor of `model`: every forward call runs on the fp16 path (view_logits).
-    flip / prob: test-time fusion of every window (fuse_window); with flip a window costs two forward passes."""
+    flip / prob: test-time fusion of every window (fuse_window); with flip a window costs two forward passes.
+    drop_percent / entropy (reliability maps): per image, on the summed scores (class weights when prob), the
+    entropy map and with drop_percent = P the labels filtered at np.percentile(entropy, P) (H.predict_reliable).  With
+    either set on_prediction receives the filtered maps and one more trailing argument, the entropy heat map (uint8, None
+    without entropy=True).  With drop_percent the return value is (mIoU, IoU, rel): mIoU / IoU are those of the unfiltered
+    arg-max as before, and rel = dict(miou_reliable, iou_reliable, miou_unreliable, iou_unreliable, coverage = kept pixels
+    over non-ignored pixels, hist_reliable, hist_unreliable = the (3, classes) integer counts) from a second confusion
+    histogram on the target with the unreliable pixels set to `ignore`; unreliable = total - reliable."""
+    H.check_drop_percent(drop_percent)
     model.eval()
     dev = next(model.parameters()).device
     hist = torch.zeros(3 * classes, dtype=torch.int64, device=dev)
+    hist_rel = torch.zeros(3 * classes, dtype=torch.int64, device=dev) if drop_percent is not None else None
     if palette is not None:
         palette = torch.as_tensor(palette).to(dev)
     for i, (image, label) in enumerate(samples):
@@ -150,7 +166,18 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
         lab = torch.as_tensor(np.asarray(label)).to(dev).long().contiguous().unsqueeze(0)
         h, w = lab.shape[1:]
         call("u2pl_confusion_hist_f32", logits.contiguous(), lab, ignore, 1, classes, h, w, hist)
-        if on_prediction is not None and palette is not None:
+        if drop_percent is not None or (entropy and on_prediction is not None):
+            dump = on_prediction is not None
+            gray, color, rel = H.predict_reliable(logits.unsqueeze(0), (h, w), prob, palette if dump else None, drop_percent,
+                                                  entropy and dump)
+            if drop_percent is not None:
+                kept = lab.clone()
+                H.drop_high_entropy_(kept, rel["entropy"], rel["threshold"], ignore)
+                call("u2pl_confusion_hist_f32", logits.contiguous(), kept, ignore, 1, classes, h, w, hist_rel)
+            if on_prediction is not None:
+                maps = [gray[0].cpu().numpy()] + ([] if color is None else [color[0].cpu().numpy()])
+                on_prediction(i, *maps, None if rel["heat"] is None else rel["heat"].cpu().numpy())
+        elif on_prediction is not None and palette is not None:
             gray, color = H.predict_map(logits.unsqueeze(0), (h, w), palette)
             on_prediction(i, gray[0].cpu().numpy(), color[0].cpu().numpy())
         elif on_prediction is not None:
@@ -158,4 +185,12 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
     hh = hist.cpu().double().reshape(3, classes)
     inter, union = hh[0], hh[1] + hh[2] - hh[0]
     iou = (inter / (union + 1e-10)).numpy()
-    return float(np.mean(iou)), iou
+    if hist_rel is None:
+        return float(np.mean(iou)), iou
+    total, reliable = hist.cpu().numpy().reshape(3, classes), hist_rel.cpu().numpy().reshape(3, classes)
+    unreliable = total - reliable
+    (mr, ir), (mu, iu) = _iou(reliable), _iou(unreliable)
+    rel = dict(miou_reliable=mr, iou_reliable=ir, miou_unreliable=mu, iou_unreliable=iu,
+               coverage=float(reliable[1].sum()) / max(float(total[1].sum()), 1.0), hist_reliable=reliable,
+               hist_unreliable=unreliable)
+    return float(np.mean(iou)), iou, rel

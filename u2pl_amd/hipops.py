@@ -2,6 +2,7 @@
 
 Everything numeric happens in libu2pl_hip.so; torch supplies device memory,
 the current HIP stream and the autograd tape (torch.autograd.Function)."""
+import math
 import os
 
 import numpy as np
@@ -106,6 +107,89 @@ def window_fuse(pred, count, logits, origin, size, flip=False, softmax=False, we
     call("u2pl_window_fuse_f32", _f32c(pred), count, C, Hh, Ww, _f32c(logits), logits.stride(0), logits.stride(1),
          logits.stride(2), logits.shape[1], logits.shape[2], int(origin[0]), int(origin[1]), int(size[0]), int(size[1]),
          int(bool(flip)), int(bool(softmax)), float(weight), int(bool(bump)))
+
+
+def predict_entropy(scores_low, size, prob=False):
+    """label and softmax entropy of every pixel of F.interpolate(scores_low, size, 'bilinear', align_corners=True) in one
+    launch -> (label uint8 (N,H,W) = predict_map's bits, entropy float32 (N,H,W)); the (N,C,H,W) scores are never written.
+    prob=False: the scores are logits, the entropy is that of their softmax (entropy_map_up's bits); prob=True: they are
+    non-negative class weights (what window_fuse(softmax=True) accumulates), normalised by their sum; a pixel whose weights
+    sum to nothing gets log(C).  scores_low may be any strided (N,C,h,w) view."""
+    _chk_cuda(scores_low)
+    N, C, h, w = scores_low.shape
+    H, W = int(size[0]), int(size[1])
+    label = torch.empty((N, H, W), dtype=torch.uint8, device=scores_low.device)
+    ent = torch.empty((N, H, W), dtype=torch.float32, device=scores_low.device)
+    call("u2pl_predict_entropy_f32", _f32c(scores_low), *_strides_nchw(scores_low), N, C, h, w, H, W, int(bool(prob)), label, ent)
+    return label, ent
+
+
+def entropy_threshold(entropy, percent):
+    """np.percentile(entropy.ravel(), percent) as a one-element float32 device tensor (a view of a fresh select workspace):
+    every pixel is valid, the workspace's two counts are set on the device and the host waits for nothing."""
+    _chk_cuda(entropy)
+    ent = _f32c(entropy).contiguous()
+    ws = new_select_ws(ent.device, ent.numel())
+    ws[0:2].fill_(ent.numel())          # n_valid = n_total; the pass-0 histogram is the select's own (ws._hist0 stays False)
+    return run_select(ent, ws, [("pct", float(percent))])
+
+
+def reliable_map(label, entropy, thr=None, palette=None, heat_classes=None):
+    """the reference's drop rule (loss_helper.py:41-43) on a uint8 label map, in place: label[entropy >= thr] = 255, then
+    rgb = palette[label] and heat = the entropy as a byte, 255 = log(heat_classes).  thr: one-element float32 device tensor
+    (entropy_threshold) or None: nothing is dropped.  -> (rgb uint8 label.shape + (3,) | None, heat uint8 | None,
+    ndropped one-element int32 device tensor | None)."""
+    _chk_cuda(label, entropy, thr, palette)
+    if label.dtype != torch.uint8 or not label.is_contiguous():
+        raise _lib.HipError("reliable_map: expected a contiguous uint8 label map (it is rewritten in place)")
+    if entropy.shape != label.shape or not entropy.is_contiguous():
+        raise _lib.HipError("reliable_map: expected a contiguous entropy map of the label map's shape")
+    dev = label.device
+    rgb = heat = ndropped = None
+    scale = 0.0
+    if heat_classes is not None:
+        if int(heat_classes) < 2:
+            raise _lib.HipError("reliable_map: the heat map needs at least two classes (255 = log(classes))")
+        scale = float(np.float32(255 / math.log(int(heat_classes))))
+        heat = torch.empty(label.shape, dtype=torch.uint8, device=dev)
+    if thr is not None:
+        if heat_classes is not None and int(heat_classes) > 255:
+            raise _lib.HipError("reliable_map: 255 is the ignore value, a threshold needs C <= 255")
+        if thr.dtype != torch.float32 or thr.numel() != 1:
+            raise _lib.HipError("reliable_map: expected a one-element float32 threshold")
+        ndropped = torch.zeros(1, dtype=torch.int32, device=dev)
+    if palette is not None:
+        if tuple(palette.shape) != (256, 3):
+            raise _lib.HipError("palette: expected shape (256, 3)")
+        palette = _u8c(palette, "palette")
+        rgb = torch.empty(tuple(label.shape) + (3,), dtype=torch.uint8, device=dev)
+    call("u2pl_reliable_map_u8", label, _f32c(entropy), thr, label.numel(), palette, rgb, heat, scale, ndropped)
+    return rgb, heat, ndropped
+
+
+def check_drop_percent(drop_percent):
+    """trainer.unsupervised.drop_percent's meaning: the share of pixels kept, a percentile in [0, 100]"""
+    if drop_percent is not None and not 0.0 <= float(drop_percent) <= 100.0:
+        raise ValueError(f"drop_percent is a percentile in [0, 100], got {drop_percent!r}")
+
+
+def predict_reliable(scores_low, size, prob=False, palette=None, drop_percent=None, heat=False):
+    """the prediction epilogue with reliability: predict_entropy, then with drop_percent = P the per-image threshold
+    np.percentile(entropy, P) (entropy_threshold; the 100 - P per cent highest-entropy pixels become 255), then reliable_map
+    for the drop, the colours and the heat bytes.  One image at a time (the threshold is per image).
+    -> (label (1,H,W), rgb (1,H,W,3) | None, dict(entropy (H,W), heat (H,W) | None, threshold | None, ndropped | None))."""
+    check_drop_percent(drop_percent)
+    N, C = scores_low.shape[:2]
+    if N != 1:
+        raise _lib.HipError("predict_reliable: one image at a time")
+    if drop_percent is not None and C > 255:
+        raise _lib.HipError("predict_reliable: 255 is the ignore value, a threshold needs C <= 255")
+    label, ent = predict_entropy(scores_low, size, prob)
+    thr = None if drop_percent is None else entropy_threshold(ent, drop_percent)
+    rgb = hmap = ndropped = None
+    if thr is not None or palette is not None or heat:
+        rgb, hmap, ndropped = reliable_map(label, ent, thr, palette, C if heat else None)
+    return label, rgb, dict(entropy=ent[0], heat=None if hmap is None else hmap[0], threshold=thr, ndropped=ndropped)
 
 
 def infer_input(img_u8_hwc, lut, size):

@@ -6,7 +6,8 @@
                                      the image size + argmax + colour lookup (one kernel): neither the resized float
                                      image on the host nor the full-resolution logits exist; half=: the forward on the
                                      fp16 path (u2pl_amd.half), redone in fp32 when it saturated; flip= / prob=: the
-                                     views fused at the image size (eval.py:166-180, commented out upstream)
+                                     views fused at the image size (eval.py:166-180, commented out upstream);
+                                     drop_percent= / entropy=: entropy map and labels filtered by it (loss_helper.py:35-43)
   colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables
 """
 import numpy as np
@@ -44,7 +45,8 @@ def normalise_lut(mean, std):
 
 
 @torch.no_grad()
-def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=False, prob=False):
+def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=False, prob=False, drop_percent=None,
+                entropy=False):
     """img_u8 (h,w,3) uint8, lut (3,256) float32, palette (256,3) uint8 or None: GPU tensors.
     -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits).
     half: a u2pl_amd.half.HalfPredictor of `model` -- the forward pass runs with fp16 activations and weights, and the
@@ -53,7 +55,14 @@ def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=F
     flip / prob (test-time fusion, evaluate.fuse_window's rule): the views -- the input and, with flip, its mirror image,
     whose result is mirrored back -- are fused straight to the image size, as class probabilities when prob, into a
     (C,h,w) accumulator (one u2pl_window_fuse_f32 launch per view), which predict_map reads at identity size; pred is then
-    that accumulator, and fell_back tells whether any view was run again."""
+    that accumulator, and fell_back tells whether any view was run again.
+    drop_percent / entropy (reliability maps): when either is set the final scores go through
+    H.predict_reliable instead of predict_map and the result gains one last element, dict(entropy (h,w) float32, heat uint8
+    (h,w) or None, threshold, ndropped: one-element device tensors or None).  drop_percent = P in [0, 100] has the meaning
+    of trainer.unsupervised.drop_percent, the share kept: the pixels whose entropy reaches np.percentile(entropy, P) become
+    255 in label and take palette[255] in rgb.  entropy=True adds the heat map (255 = log C) and leaves label / rgb as they
+    are without it."""
+    H.check_drop_percent(drop_percent)
     h, w = img_u8.shape[:2]
     x = H.infer_input(img_u8, lut, input_scale)
     fell_back = False
@@ -75,6 +84,12 @@ def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=F
         if flip:
             H.window_fuse(fused, None, forward(x.flip(3)), (0, 0), (h, w), True, prob, weight, False)
         pred = fused.unsqueeze(0)
-    label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
+    rel = None
+    if drop_percent is not None or entropy:
+        label, rgb, rel = H.predict_reliable(pred, (h, w), prob, palette, drop_percent, entropy)
+    else:
+        label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
     out = (label[0], None if rgb is None else rgb[0], pred)
-    return out if half is None else out + (fell_back,)
+    if half is not None:
+        out += (fell_back,)
+    return out if rel is None else out + (rel,)
