@@ -627,6 +627,57 @@ int u2pl_hgap_f16(const unsigned short* x, long ldx, int N, int HW, int C, unsig
 int u2pl_hbilinear_f16(const unsigned short* x, long ldx, int N, int h, int w, int C, unsigned short* y, long ldy,
                        int H, int W, hipStream_t stream);
 
+/* ---- more than 32 classes (reliability.hip, contrast_wide.hip) -----------------------------------------------------
+ * The entry points above keep a pixel's multi-hot label in ONE 32-bit word (C <= 32).  These take 1 <= C <= 255 (label
+ * value 255 is the ignore value; U2PL_EINVAL otherwise): class bits are WORD PLANES, u32 [W][P] with
+ * W = u2pl_wide_words(C) = ceil(C / 32), plane g = classes 32 g .. 32 g + 31, P = pixels of the concatenated low-res
+ * batch.  Counts are u32 [3][C] (kind 0 anchors, 1 low-valid, 2 negative keys), and the pixel lists live in ONE flat
+ * int32 buffer, back to back in (kind, class) order, each in row-major pixel order; offsets int64 [3][C] = first element
+ * of every list.  The caller reads counts back, allocates the flat buffer (sum of the counts) and then has the lists
+ * written. */
+int u2pl_wide_words(int C);
+/* label_onehot (utils.py:50-59, slot-0 quirk) + masks + legacy-nearest down-sampling: train_semi.py:408-465; the forms
+ * of u2pl_reliability_masks / u2pl_reliability_apply with lbits as planes [W][2B*h*w] */
+int u2pl_reliability_masks_wide(const float* entropy, const unsigned* thr_lo_bits, const unsigned* thr_hi_bits,
+                                const long long* label_l, const long long* label_u, int ignore, int B, int H, int W,
+                                int h, int w, int negative_high_entropy, int C, float* low_mask, float* high_mask,
+                                unsigned* lbits, hipStream_t stream);
+int u2pl_reliability_apply_wide(const float* entropy, const unsigned* thr_bits, const long long* label_l,
+                                const long long* label_u, int ignore, int B, int H, int W, int h, int w,
+                                int negative_high_entropy, int C, long long* target_u, unsigned* nkept, float* low_mask,
+                                float* high_mask, unsigned* lbits, hipStream_t stream);
+/* (N,C,h,w) int64 multi-hot (the label_l / label_u arguments of compute_contra_memobank_loss, loss_helper.py:51-66)
+ * <-> planes [W][N*h*w] */
+int u2pl_pack_class_bits_wide(const long long* onehot, int N, int C, int h, int w, unsigned* bits, hipStream_t stream);
+int u2pl_unpack_class_bits_wide(const unsigned* bits, int N, int C, int h, int w, long long* onehot, hipStream_t stream);
+/* loss_helper.py:103-141: the masks of u2pl_contra_classify as planes (rank over the pixel's whole row of C
+ * probabilities, ties towards the lower class index), then the list lengths (counts) and list offsets.  workspace:
+ * u2pl_contra_wide_workspace_bytes(P, C) bytes, handed on to u2pl_compact_lists_wide.  A block owns
+ * u2pl_contra_wide_block_pixels(C) pixels (256 up to C = 47, 128 up to 93, else 64). */
+size_t u2pl_contra_wide_workspace_bytes(long P, int C);
+int u2pl_contra_wide_block_pixels(int C);
+/* 1: contiguous [pixel][C] probability rows are staged in LDS (C <= 183); 0: every thread reads its row from memory */
+int u2pl_contra_wide_staged(int C);
+int u2pl_contra_classify_wide(const float* prob, long sn, long sc, long sp, const unsigned* lbits, const float* low_mask,
+                              const float* high_mask, int N2, int num_labeled, int C, int h, int w, float thr_p,
+                              float thr_n, int low_rank, int high_rank, unsigned* abits, unsigned* lowbits,
+                              unsigned* nbits, void* workspace, unsigned* counts, long long* offsets,
+                              hipStream_t stream);
+/* boolean-mask indexing order (loss_helper.py:115-116,119-123,142) for all three kinds into idx int32 [idx_len] */
+int u2pl_compact_lists_wide(const unsigned* abits, const unsigned* lowbits, const unsigned* nbits, long P, int C,
+                            const void* workspace, const long long* offsets, int* idx, long idx_len,
+                            hipStream_t stream);
+/* torch.mean(rep_teacher[low_valid], dim=0): loss_helper.py:119-123, ordered double-precision sums over the
+ * low-valid lists; proto float [C][D], NaN rows for classes without members */
+int u2pl_class_prototypes_wide(const float* rows, long ld, int D, const int* idx, const long long* offsets,
+                               const unsigned* counts, int C, float* proto, hipStream_t stream);
+/* dequeue_and_enqueue (utils.py:27-47) on the device-resident bank of u2pl_bank_init / u2pl_bank_enqueue_f32 (same
+ * state layout): class c appends rows[idx[list_off_dev[c] + j]], j < counts_dev[c] */
+int u2pl_bank_init_wide(long long* state, int C, const long long* caps_host, hipStream_t stream);
+int u2pl_bank_enqueue_wide_f32(long long* state, float* storage, int D, const float* rows, long ld, const int* idx,
+                               const long long* list_off_dev, const long long* row_start_dev,
+                               const unsigned* counts_dev, int C, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,22 @@ from ._lib import call, query
 
 SEL_WORD_VAL = 40
 SEL_WORD_THR = 56
-MAXC = 32
+MAXC = 32          # the narrow route: a pixel's class bits in one 32-bit word (csrc/contrast.hip)
+WIDE_MAXC = 255    # the wide route: class bits as word planes (csrc/contrast_wide.hip); label value 255 is the ignore value
+
+
+def wide_words(C):
+    """32-bit planes that hold the class bits of C classes"""
+    return (int(C) + 31) // 32
+
+
+def check_num_classes(C, what="num_classes"):
+    """2 .. 255 classes train; more cannot, labels are bytes and 255 is the ignore value"""
+    if int(C) > WIDE_MAXC:
+        raise ValueError(f"{what} = {int(C)}: too many classes, at most {WIDE_MAXC} are supported "
+                         "(label value 255 is the ignore value)")
+    if int(C) < 1:
+        raise ValueError(f"{what} = {int(C)}: expected a positive class count")
 
 
 def _f32c(x):
@@ -292,9 +307,13 @@ def entropy_map_up(logits_low, size, label, ws, ignore=255):
     return ent
 
 
-def reliability_apply(entropy, thr3, label_l, label_u_aug, out_hw, negative_high_entropy=True, ignore=255):
+def reliability_apply(entropy, thr3, label_l, label_u_aug, out_hw, negative_high_entropy=True, ignore=255,
+                      num_classes=None):
     """fused: unsup target (label_u_aug with entropy >= thr3[0] -> 255), low/high masks
-    (thr3[1], thr3[2]) at out_hw and the Q0 class bits; returns (target_u, nkept, low, high, lbits)."""
+    (thr3[1], thr3[2]) at out_hw and the Q0 class bits; returns (target_u, nkept, low, high, lbits).
+    num_classes > 32: lbits are word planes (W, 2B, h, w).  WARNING: num_classes=None means AT MOST 32 CLASSES -- one
+    32-bit word per pixel; a label >= 32 would then alias onto a lower bit.  Pass num_classes whenever the labels can reach
+    32 or more (reliability_split always does)."""
     B, H, W = label_u_aug.shape
     h, w = out_hw
     dev = entropy.device
@@ -302,6 +321,12 @@ def reliability_apply(entropy, thr3, label_l, label_u_aug, out_hw, negative_high
     nk = torch.zeros(1, dtype=torch.int32, device=dev)
     low = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
     high = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
+    if num_classes is not None and int(num_classes) > MAXC:
+        check_num_classes(num_classes)
+        lbits = torch.empty((wide_words(num_classes), 2 * B, h, w), dtype=torch.int32, device=dev)
+        call("u2pl_reliability_apply_wide", entropy, thr3, label_l.contiguous(), label_u_aug.contiguous(), ignore, B, H, W, h,
+             w, int(bool(negative_high_entropy)), int(num_classes), target, nk, low, high, lbits)
+        return target, nk, low, high, lbits
     lbits = torch.empty((2 * B, h, w), dtype=torch.int32, device=dev)
     call("u2pl_reliability_apply", entropy, thr3, label_l.contiguous(), label_u_aug.contiguous(), ignore, B, H, W, h, w,
          int(bool(negative_high_entropy)), target, nk, low, high, lbits)
@@ -375,7 +400,8 @@ def reliability_split(logits_low, size, label_l, label_u_aug, out_hw, percents, 
         thr = run_select(ent, ws, [("pct", float(p)) for p in percents])
         if nspec == 3:
             target, _, low, high, lbits = reliability_apply(ent, thr, label_l, label_u_aug, (hm, wm),
-                                                            negative_high_entropy=negative_high_entropy, ignore=ignore)
+                                                            negative_high_entropy=negative_high_entropy, ignore=ignore,
+                                                            num_classes=C)
         else:
             target = label_u_aug.clone()
             drop_high_entropy_(target, ent, thr[0:1], ignore)
@@ -539,28 +565,50 @@ def drop_high_entropy_(target, entropy, thr_bits, ignore=255):
 
 
 def reliability_masks(entropy, thr_lo, thr_hi, label_l, label_u_aug, out_hw, negative_high_entropy=True,
-                      ignore=255):
+                      ignore=255, num_classes=None):
     """train_semi.py:408-465 -> low_mask_all, high_mask_all (2B,1,h,w) float and
-    the (quirky) multi-hot labels as class bitmasks (2B,h,w) int32."""
+    the (quirky) multi-hot labels as class bitmasks (2B,h,w) int32; num_classes > 32: word planes (W,2B,h,w).
+    WARNING: num_classes=None means AT MOST 32 CLASSES (one word per pixel; a label >= 32 would alias onto a lower bit):
+    pass num_classes whenever the labels can reach 32 or more."""
     B, H, W = label_u_aug.shape
     h, w = out_hw
     dev = entropy.device
     low = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
     high = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
+    if num_classes is not None and int(num_classes) > MAXC:
+        check_num_classes(num_classes)
+        lbits = torch.empty((wide_words(num_classes), 2 * B, h, w), dtype=torch.int32, device=dev)
+        call("u2pl_reliability_masks_wide", entropy, thr_lo, thr_hi, label_l.contiguous(), label_u_aug.contiguous(),
+             ignore, B, H, W, h, w, int(bool(negative_high_entropy)), int(num_classes), low, high, lbits)
+        return low, high, lbits
     lbits = torch.empty((2 * B, h, w), dtype=torch.int32, device=dev)
     call("u2pl_reliability_masks", entropy, thr_lo, thr_hi, label_l.contiguous(), label_u_aug.contiguous(),
          ignore, B, H, W, h, w, int(bool(negative_high_entropy)), low, high, lbits)
     return low, high, lbits
 
 
-def pack_class_bits(onehot):
+def pack_class_bits(onehot, wide=None):
+    """(N,C,h,w) multi-hot -> class bits (N,h,w) int32; C > 32 (or wide=True, for tests): word planes (W,N,h,w)"""
     N, C, h, w = onehot.shape
+    if C > MAXC if wide is None else wide:
+        check_num_classes(C)
+        bits = torch.empty((wide_words(C), N, h, w), dtype=torch.int32, device=onehot.device)
+        call("u2pl_pack_class_bits_wide", onehot.long().contiguous(), N, C, h, w, bits)
+        return bits
     bits = torch.empty((N, h, w), dtype=torch.int32, device=onehot.device)
     call("u2pl_pack_class_bits", onehot.long().contiguous(), N, C, h, w, bits)
     return bits
 
 
 def unpack_class_bits(bits, C):
+    if bits.dim() == 4:      # word planes (W,N,h,w)
+        check_num_classes(C)
+        if bits.shape[0] != wide_words(C):
+            raise _lib.HipError(f"unpack_class_bits: {C} classes are {wide_words(C)} planes, got {bits.shape[0]}")
+        _, N, h, w = bits.shape
+        oh = torch.empty((N, C, h, w), dtype=torch.int64, device=bits.device)
+        call("u2pl_unpack_class_bits_wide", bits.contiguous(), N, C, h, w, oh)
+        return oh
     N, h, w = bits.shape
     oh = torch.empty((N, C, h, w), dtype=torch.int64, device=bits.device)
     call("u2pl_unpack_class_bits", bits, N, C, h, w, oh)
@@ -574,6 +622,7 @@ class DeviceMemoryBank:
     of class c lives at physical slot (head[c] + j) % cap[c]."""
 
     def __init__(self, num_classes, queue_size, feat_dim=256, device="cuda"):
+        check_num_classes(num_classes, "DeviceMemoryBank: num_classes")
         self.C, self.D = num_classes, feat_dim
         self.cap = [int(q) for q in queue_size]
         # ONE storage buffer, the class rings are row ranges of it (u2pl_bank_* address it through the device state)
@@ -601,11 +650,18 @@ class DeviceMemoryBank:
             self._state_stale = False
         return True
 
-    def enqueue_device(self, rows, ld, idx, idx_stride, counts_dev):
+    def enqueue_device(self, rows, ld, idx, idx_stride, counts_dev, list_off=None):
         """dequeue_and_enqueue for every class in ONE call with the list lengths still on the DEVICE (counts_dev: uint32
         [C]): can be issued before the step's host synchronisation.  Follow with mirror_counts() once the counts are on
-        the host."""
+        the host.  list_off (int64 [C] on the device): idx is a flat list buffer and class c's list starts at
+        list_off[c] (the wide route; any C up to 255)."""
         self._sync_state()
+        if list_off is not None or self.C > MAXC:
+            if list_off is None:
+                raise _lib.HipError("enqueue_device: more than 32 classes need the flat list layout (list_off)")
+            call("u2pl_bank_enqueue_wide_f32", self.state, self.storage, self.D, rows, ld, idx, list_off, None, counts_dev,
+                 self.C)
+            return
         call("u2pl_bank_enqueue_f32", self.state, self.storage, self.D, rows, ld, idx, idx_stride, None, counts_dev, self.C)
         if REPLAY is not None:
             REPLAY["enqueue"] = (rows, ld, idx, idx_stride, counts_dev)
@@ -696,13 +752,94 @@ class DeviceMemoryBank:
 
 # --------------------------------------------------------------------------- contrastive core
 class ContraPhase1:
-    """Outputs of phase 1 (loss_helper.py:80-154) living on the device."""
-    __slots__ = ("idx", "counts", "proto", "cap", "counts_host")
+    """Outputs of phase 1 (loss_helper.py:80-154) living on the device.
+    Narrow route (C <= 32): idx int32 (3, 32, P), counts (3, 32).  Wide route: counts (3, C), offsets int64 (3, C) and,
+    once finish() has run with the counts on the host, idx = ONE flat int32 buffer with the lists back to back in
+    (kind, class) order.  list() / list_ptr() / lists() address a list the same way on both."""
+    __slots__ = ("idx", "counts", "proto", "cap", "counts_host", "wide", "C", "offsets", "offsets_host", "bits", "_fin")
+
+    def list_ptr(self, kind, c):
+        """device address of the first element of list (kind, c)"""
+        if self.wide:
+            return self.idx.data_ptr() + int(self.offsets_host[kind][c]) * 4
+        return self.idx.data_ptr() + (kind * MAXC + c) * self.cap * 4
+
+    def list(self, kind, c):
+        """the pixel list (kind, c) as an int32 view (needs counts_host)"""
+        n = int(self.counts_host[kind][c])
+        if self.wide:
+            o = int(self.offsets_host[kind][c])
+            return self.idx[o:o + n]
+        return self.idx[kind, c, :n]
+
+    def lists(self, kind):
+        """what enqueue_all_classes indexes by class: the narrow (32, P) plane, or the wide route's per-class views"""
+        if self.wide:
+            return [self.list(kind, c) for c in range(self.C)]
+        return self.idx[kind]
+
+    def finish(self, counts_host):
+        """wide route: with the list lengths on the host, size the flat list buffer, write the lists and the prototypes
+        (the narrow route did all of it in contra_phase1)"""
+        self.counts_host = counts_host
+        if not self.wide or self._fin is None:
+            return
+        rows, ld, D, P, work = self._fin
+        self._fin = None
+        cnt = np.asarray(counts_host, dtype=np.int64)[:, :self.C]
+        self.offsets_host = wide_list_offsets(cnt)
+        total = int(cnt.sum())
+        self.idx = torch.empty(max(total, 1), dtype=torch.int32, device=self.counts.device)
+        abits, lowbits, nbits = self.bits
+        call("u2pl_compact_lists_wide", abits, lowbits, nbits, P, self.C, work, self.offsets, self.idx, total)
+        call("u2pl_class_prototypes_wide", rows, ld, D, self.idx, self.offsets, self.counts, self.C, self.proto)
+
+
+def wide_list_offsets(counts):
+    """counts [3][C] -> first element of every list in the flat buffer (lists back to back in (kind, class) order): the
+    host's copy of what u2pl_contra_classify_wide writes to `offsets`"""
+    cnt = np.asarray(counts, dtype=np.int64)
+    flat = cnt.reshape(-1)
+    return (np.cumsum(flat) - flat).reshape(cnt.shape)
+
+
+def _contra_phase1_wide(rep_teacher_rows, ld, D, prob, prob_strides, lbits, low_mask, high_mask, num_labeled, C, h, w, cfg):
+    """the wide route up to the list lengths: classify into word planes, scan, offsets.  ContraPhase1.finish() writes
+    the lists and the prototypes once the lengths are on the host."""
+    check_num_classes(C)
+    dev = lbits.device
+    W = wide_words(C)
+    if lbits.dim() == 3:     # one 32-bit word per pixel (C <= 32 forced onto this route): it is plane 0
+        lbits = lbits.unsqueeze(0)
+    if lbits.shape[0] != W:
+        raise _lib.HipError(f"contra_phase1: {C} classes need {W} planes of class bits, got {lbits.shape[0]}")
+    lbits = lbits.contiguous()
+    N2 = lbits.shape[1]
+    P = N2 * h * w
+    bits = torch.empty((3, W, P), dtype=torch.int32, device=dev)
+    out = ContraPhase1()
+    out.wide, out.C, out.cap = True, C, P
+    out.counts = torch.empty((3, C), dtype=torch.int32, device=dev)
+    out.offsets = torch.empty((3, C), dtype=torch.int64, device=dev)
+    out.proto = torch.empty((C, D), dtype=torch.float32, device=dev)
+    out.idx = out.offsets_host = out.counts_host = None
+    work = torch.empty(query("u2pl_contra_wide_workspace_bytes", P, C), dtype=torch.uint8, device=dev)
+    call("u2pl_contra_classify_wide", prob, *prob_strides, lbits, low_mask, high_mask, N2, num_labeled, C, h, w,
+         float(cfg["current_class_threshold"]), float(cfg["current_class_negative_threshold"]), int(cfg["low_rank"]),
+         int(cfg["high_rank"]), bits[0], bits[1], bits[2], work, out.counts, out.offsets)
+    out.bits = (bits[0], bits[1], bits[2])
+    out._fin = (rep_teacher_rows, ld, D, P, work)
+    return out
 
 
 def contra_phase1(rep_teacher_rows, ld, D, prob, prob_strides, lbits, low_mask, high_mask, num_labeled, C, h, w,
-                  cfg):
-    """classify + compaction + prototypes.  prob_strides = (sn, sc, sp)."""
+                  cfg, wide=None):
+    """classify + compaction + prototypes.  prob_strides = (sn, sc, sp).
+    C > 32 takes the wide route (csrc/contrast_wide.hip): the lists and prototypes are written by the returned object's
+    finish(counts_host).  wide=True forces that route at C <= 32 -- for tests that compare the two; not a tuning knob."""
+    if C > MAXC if wide is None else wide:
+        return _contra_phase1_wide(rep_teacher_rows, ld, D, prob, prob_strides, lbits, low_mask, high_mask, num_labeled, C,
+                                   h, w, cfg)
     if REPLAY is not None:
         REPLAY["phase1"] = (rep_teacher_rows, ld, D, prob, prob_strides, lbits, low_mask, high_mask, num_labeled, C, h, w, cfg)
     dev = lbits.device
@@ -713,6 +850,7 @@ def contra_phase1(rep_teacher_rows, ld, D, prob, prob_strides, lbits, low_mask, 
     nbits = torch.empty(P, dtype=torch.int32, device=dev)
     out = ContraPhase1()
     out.cap = P
+    out.wide, out.C, out.offsets, out.offsets_host, out.bits, out._fin = False, C, None, None, (abits, lowbits, nbits), None
     out.idx = torch.empty((3, MAXC, P), dtype=torch.int32, device=dev)
     out.counts = torch.empty((3, MAXC), dtype=torch.int32, device=dev)
     out.proto = torch.empty((C, D), dtype=torch.float32, device=dev)
@@ -757,7 +895,9 @@ def _nce_forward(st, rep_rows, jobs_dev, njobs, Q, K, temp, valid_seg, groups, l
     """the forward launches: ONE (u2pl_infonce_fused_f32: InfoNCE + loss reduction + clearing of the rows the previous
     backward wrote) when the shape allows it, else u2pl_infonce_f32 + u2pl_infonce_reduce_f32 (rows cleared in backward)"""
     P, D = rep_rows.shape
-    if NCE_FUSED and Q % 4 == 0 and D <= 256:
+    # (the fused launch is exercised and sized for the narrow route's <= 32 jobs; more jobs take the separate entry points,
+    # which are generic in njobs and reduce in the same order)
+    if NCE_FUSED and Q % 4 == 0 and D <= 256 and njobs <= MAXC:
         need = query("u2pl_infonce_fused_workspace_bytes", njobs, Q)
         if st["ws"] is None or st["ws"].numel() < need:
             st["ws"] = torch.zeros(max(need, query("u2pl_infonce_fused_workspace_bytes", MAXC, Q)), dtype=torch.uint8,
@@ -905,7 +1045,7 @@ def infonce_loss(rep_rows, ph1, bank, valid_classes, counts_host, cfg, randint=N
     jb = np.zeros((len(jobs), 7), dtype=np.int64)
     off = 0
     for j, (i, vc) in enumerate(jobs):
-        jb[j, 0] = ph1.idx.data_ptr() + (0 * MAXC + i) * ph1.cap * 4
+        jb[j, 0] = ph1.list_ptr(0, i)         # Q1: the anchor list of class i = the POSITION in valid_classes, not of vc
         jb[j, 1] = base + off * 8
         jb[j, 2] = base + (off + Q) * 8
         jb[j, 3] = ph1.proto.data_ptr() + i * D * 4

@@ -100,6 +100,7 @@ def classmix(image, label, conf, sel):
 class SemiTrainer:
     def __init__(self, cfg, model, model_teacher, sup_loss_fn, steps_per_epoch, memobank=None):
         self.cfg = cfg
+        H.check_num_classes(cfg["net"]["num_classes"], "net.num_classes")      # before anything is built: at most 255 classes
         self.model, self.teacher = model, model_teacher
         self.sup_loss_fn = sup_loss_fn
         self.steps_per_epoch = steps_per_epoch
@@ -432,6 +433,7 @@ class SupTrainer:
 
     def __init__(self, cfg, model, sup_loss_fn, steps_per_epoch):
         self.cfg, self.model, self.sup_loss_fn, self.steps_per_epoch = cfg, model, sup_loss_fn, steps_per_epoch
+        H.check_num_classes(cfg["net"]["num_classes"], "net.num_classes")
         tr = cfg["trainer"]
         self.epochs = tr["epochs"]
         self._init_schedule(tr)

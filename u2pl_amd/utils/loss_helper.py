@@ -70,19 +70,23 @@ def contra_memobank_core(rep, lbits, num_labeled, prob_l, prob_u, low_mask, high
                               num_labeled, C, h, w, cfg)
         from .. import nn as K      # (late: nn imports nothing from here, but keep the module graph acyclic at import time)
         device_enqueue = not K.dist_active() and rep.is_cuda and isinstance(memobank, H.DeviceMemoryBank) and DEVICE_ENQUEUE
-        if device_enqueue:
+        if device_enqueue and not ph1.wide:
             # single rank: the keys are appended by the device-resident bank from the list lengths ON THE DEVICE, i.e.
             # before (and under) the host synchronisation below instead of after it
             memobank.enqueue_device(rep_t_rows, D, ph1.idx[2], ph1.cap, ph1.counts[2])
         # the ONE host sync of the step: the RNG bounds live on the host (loss_helper.py:179-196).  Under a process group
         # the ranks' key counts ride along (gathered on the device first), so the key exchange needs no second sync.
         counts, all_neg = exchange_counts(ph1.counts, C)
-        ph1.counts_host = counts
+        # (more than 32 classes: the flat list buffer is sized by these lengths, so the lists, the prototypes and a device
+        # enqueue are issued here, behind the read, instead of in front of it)
+        ph1.finish(counts)
         if device_enqueue:
+            if ph1.wide:
+                memobank.enqueue_device(rep_t_rows, D, ph1.idx, 0, ph1.counts[2], list_off=ph1.offsets[2])
             memobank.mirror_counts(counts[2])
             new_keys = [int(counts[2][c]) for c in range(C)]
         else:
-            new_keys = enqueue_all_classes(memobank, rep_t_rows, D, ph1.idx[2], counts[2], C, all_counts=all_neg)
+            new_keys = enqueue_all_classes(memobank, rep_t_rows, D, ph1.lists(2), counts[2], C, all_counts=all_neg)
     valid_classes = [i for i in range(C) if counts[1][i] > 0]
     LAST_STATS.update(n_keys=int(sum(new_keys)), valid_seg=len(valid_classes), njobs=0,
                       Q=int(cfg["num_queries"]), K=int(cfg["num_negatives"]))
@@ -100,6 +104,7 @@ def compute_contra_memobank_loss(rep, label_l, label_u, prob_l, prob_u, low_mask
     if momentum_prototype is not None:
         raise NotImplementedError("anchor_ema path divides by zero upstream (SURVEY Q4); not supported")
     num_labeled = label_l.shape[0]
+    H.check_num_classes(prob_l.shape[1], "compute_contra_memobank_loss: num_classes")
     lbits = H.pack_class_bits(torch.cat((label_l, label_u)))
     bank, writeback = memobank, False
     if not isinstance(memobank, H.DeviceMemoryBank):  # reference-style list of [cpu tensor]

@@ -56,8 +56,9 @@ BLOCKED_S = [0.0]
 
 
 def exchange_counts(counts_dev, C):
-    """phase-1 list lengths (u32 [3][32] on the device) -> host (this rank's [3][32]) and, under a process group, every
-    rank's negative-key counts [W][C]: the all-gather runs on the device BEFORE the single device-to-host copy."""
+    """phase-1 list lengths (u32 [3][32] on the device; [3][C] with more than 32 classes) -> host (this rank's, same
+    shape) and, under a process group, every rank's negative-key counts [W][C]: the all-gather runs on the device BEFORE
+    the single device-to-host copy.  Every rank has the same C, so the gathered blocks have one shape."""
     W = _world()
     t0 = time.perf_counter()
     try:
@@ -66,7 +67,7 @@ def exchange_counts(counts_dev, C):
         outs = [torch.empty_like(counts_dev) for _ in range(W)]
         _note("key_allgather", counts_dev.numel())
         dist.all_gather(outs, counts_dev)
-        host = torch.stack(outs).cpu().numpy()                   # [W][3][32]: the one sync
+        host = torch.stack(outs).cpu().numpy()                   # [W][3][32 or C]: the one sync
         return host[dist.get_rank()], host[:, 2, :C].astype(np.int64)
     finally:
         BLOCKED_S[0] += time.perf_counter() - t0
@@ -75,7 +76,7 @@ def exchange_counts(counts_dev, C):
 def enqueue_all_classes(bank, rows, ld, idx, counts_c, C, all_counts=None):
     """dequeue_and_enqueue for every class of one step (loss_helper.py:143-150 -> utils.py:27-47) with ONE
     count exchange and ONE padded key all-gather instead of a barrier + two object collectives per class.
-    idx[c]: int32 pixel list of class c, counts_c[c]: its length; all_counts: [W][C] from exchange_counts (saves the
+    idx[c]: int32 pixel list of class c (a (32, P) plane or a sequence of C views), counts_c[c]: its length; all_counts: [W][C] from exchange_counts (saves the
     exchange + host sync here).  Returns the gathered batch size per class."""
     W = _world()
     D = bank.D
