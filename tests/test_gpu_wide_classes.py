@@ -217,7 +217,7 @@ def test_wide_stages_equal_the_numpy_restatement(C, B, s):
     assert lbits.shape == (WR.words(C), 2 * B, s, s)
     oh_l = R.nearest_down(R.label_onehot_quirk(k["lab_l"], C), s, s)
     oh_u = R.nearest_down(R.label_onehot_quirk(k["lab_u"], C), s, s)
-    want_planes = WR.planes_from_onehot(np.concatenate([oh_l, oh_u]))
+    want_planes = WR.label_planes(k["lab_l"], k["lab_u"], C, s)
     assert np.array_equal(lbits.cpu().numpy().view(np.uint32), want_planes)
     assert int(np.concatenate([oh_l, oh_u]).sum(1).max()) >= 2            # a union of labels on one pixel
     # the fused tail writes the same bits; pack / unpack round-trip
@@ -342,6 +342,150 @@ def test_forced_wide_route_equals_the_narrow_route(C, monkeypatch):
         assert a["new_keys"] == list(g["s0_new_keys"]) == b["new_keys"]
         assert abs(b["loss"] - float(g["s0_loss"])) < 1e-4 * max(1.0, abs(float(g["s0_loss"])))
         assert np.abs(b["grad"] - g["s0_grad_rep"]).max() < 1e-5 * max(1.0, float(np.abs(g["s0_grad_rep"]).max()))
+
+
+# ------------------------------------------------------------------ 3b. one body, two instantiations
+# The reliability stages, pack / unpack and the device-resident bank are ONE implementation each, instantiated for one word
+# of class bits per pixel (C <= 32) and for word planes / the flat list buffer.  Where both are defined they must agree
+# bit for bit, and with a third party (tests/wide_ref.py, the host mirror, a FIFO of torch rows): a bug shared by both
+# instantiations still shows.
+SHARED_C = [1, 19, 31, 32]
+_BODY_CASES = {}
+
+
+def _body_case(C, B, S, s):
+    """inputs shared by the tests below (built once per shape, never modified): labels from [0, C) with ignore pixels in
+    batch slot 0 (own ignore: no bits) and in slot 1 only (counts as class 0 in slot 0, Q0), the last class present"""
+    key = (C, B, S, s)
+    if key not in _BODY_CASES:
+        rng = np.random.default_rng(7000 + 100 * C + 10 * B + s)
+        lab_l, lab_u = (rng.integers(0, C, size=(B, S, S)).astype(np.int64) for _ in range(2))
+        lab_l[:, :3] = 255
+        lab_l[1, 10:14, 5:9] = 255
+        lab_u[0, S // 2:S // 2 + 3] = 255
+        lab_u[B - 1, :, -4:] = 255
+        lab_l[0, -8:, -8:], lab_u[1, -8:, -8:] = C - 1, C - 1
+        ent = rng.random((B, S, S)).astype(np.float32)
+        ent[lab_u == 255] = np.nan
+        for lab in (lab_l, lab_u):        # the ignore pixels survive the down-sampling, in slot 0 and in another slot alone
+            small = R.nearest_down(lab, s, s)
+            assert (small[0] == 255).any() and ((small[1:] == 255).any(0) & (small[0] != 255)).any()
+        thr3 = np.array([0.9, 0.45, 0.6], np.float32)          # drop, low, high
+        _BODY_CASES[key] = dict(lab_l=lab_l, lab_u=lab_u, ent=ent, thr3=thr3, planes=WR.label_planes(lab_l, lab_u, C, s))
+    return _BODY_CASES[key]
+
+
+@pytest.mark.parametrize("C", SHARED_C)
+@pytest.mark.parametrize("B", [2, 3])
+@pytest.mark.parametrize("S,s", [(17, 5), (65, 17)])
+def test_reliability_stages_one_word_and_plane_forms_agree(C, B, S, s):
+    """u2pl_reliability_apply / _masks against their _wide entries on the same inputs: target_u, nkept, low_mask and
+    high_mask bit-equal, plane 0 of the wide lbits == the one-word lbits == tests/wide_ref.py's restatement (bit 31 set
+    at C = 32); the target also against numpy.  apply runs with negative_high_entropy = 1, masks with 0."""
+    H = hip()
+    k = _body_case(C, B, S, s)
+    ent, thr3, lab_l, lab_u = T(k["ent"]), T(k["thr3"]), T(k["lab_l"]), T(k["lab_u"])
+    n = 2 * B * s * s
+
+    def outputs(planes):
+        f = lambda: torch.full((2 * B, 1, s, s), -7.0, device=DEV)
+        return (torch.full((B, S, S), -7, dtype=torch.int64, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV), f(), f(),
+                torch.full((planes, n) if planes else (n,), -7, dtype=torch.int32, device=DEV))
+    tn, kn, lown, highn, bitsn = outputs(0)
+    tw, kw, loww, highw, bitsw = outputs(1)
+    H.call("u2pl_reliability_apply", ent, thr3, lab_l, lab_u, 255, B, S, S, s, s, 1, tn, kn, lown, highn, bitsn)
+    H.call("u2pl_reliability_apply_wide", ent, thr3, lab_l, lab_u, 255, B, S, S, s, s, 1, C, tw, kw, loww, highw, bitsw)
+    want = k["planes"].reshape(1, n)
+    assert torch.equal(tn, tw) and torch.equal(kn, kw) and torch.equal(lown, loww) and torch.equal(highn, highw)
+    assert torch.equal(bitsw[0], bitsn)
+    assert np.array_equal(bitsn.cpu().numpy().view(np.uint32), want[0])
+    assert np.array_equal(bitsw.cpu().numpy().view(np.uint32), want)
+    if C == 32:
+        assert (bitsn.cpu().numpy().view(np.uint32) >> np.uint32(31)).any()
+    with np.errstate(invalid="ignore"):
+        t_want = np.where(k["ent"] >= k["thr3"][0], 255, k["lab_u"])
+    assert np.array_equal(tn.cpu().numpy(), t_want) and int(kn) == int((t_want != 255).sum()) and 0 < int(kn) < t_want.size
+    assert 0 < float(lown.sum()) < n and 0 < float(highn.sum()) < n
+    _, _, low2n, high2n, bits2n = outputs(0)
+    _, _, low2w, high2w, bits2w = outputs(1)
+    H.call("u2pl_reliability_masks", ent, thr3[1:2], thr3[2:3], lab_l, lab_u, 255, B, S, S, s, s, 0, low2n, high2n, bits2n)
+    H.call("u2pl_reliability_masks_wide", ent, thr3[1:2], thr3[2:3], lab_l, lab_u, 255, B, S, S, s, s, 0, C, low2w, high2w,
+           bits2w)
+    assert torch.equal(low2n, low2w) and torch.equal(high2n, high2w) and torch.equal(bits2w[0], bits2n)
+    assert torch.equal(bits2n, bitsn) and torch.equal(low2n, lown)
+    assert torch.equal(high2n[:B], highn[:B]) and bool((high2n[B:] == 1).all())       # negative_high_entropy = 0: all ones
+
+
+@pytest.mark.parametrize("C", SHARED_C)
+def test_pack_and_unpack_one_word_and_plane_forms_agree(C):
+    """pack_class_bits(wide=False) against wide=True (three blocks of pixels): the one plane == the word == the numpy
+    planes, and unpack of either returns the input"""
+    H = hip()
+    gen = torch.Generator(device=DEV).manual_seed(C)
+    oh = (torch.rand(3, C, 17, 17, device=DEV, generator=gen) < 0.3).long()
+    oh[0, C - 1, 0, 0] = 1
+    narrow, wide = H.pack_class_bits(oh, wide=False), H.pack_class_bits(oh, wide=True)
+    assert narrow.shape == (3, 17, 17) and wide.shape == (1, 3, 17, 17)
+    assert torch.equal(wide[0], narrow)
+    assert np.array_equal(wide.cpu().numpy().view(np.uint32), WR.planes_from_onehot(oh.cpu().numpy()))
+    assert torch.equal(H.unpack_class_bits(narrow, C), oh) and torch.equal(H.unpack_class_bits(wide, C), oh)
+
+
+@pytest.mark.parametrize("C", [1, 19, 32])
+def test_bank_entries_for_32_and_255_classes_agree(C):
+    """u2pl_bank_init / u2pl_bank_enqueue_f32 on a [C][stride] list array against the _wide entries on the same array
+    flattened with list_off[c] = c * stride: state and storage bit-equal after init and after each of three enqueues
+    whose counts cover 0, exactly cap, more than cap (only the last cap rows survive) and a wrap of the ring, then one
+    enqueue with idx = NULL and row_start; both equal the host mirror (head, length, pointer) and a FIFO of torch rows."""
+    H = hip()
+    D, stride, nrows = 8, 70, 200
+    caps = [(3, 5, 64)[c % 3] for c in range(C)]
+    seq = lambda c, cap: ([0, cap + 2, cap], [cap - 1, 2, cap + 3], [cap, 0, cap - 1])[(c // 3) % 3]
+    steps = [[seq(c, caps[c])[i] for c in range(C)] for i in range(3)]
+    assert 0 in sum(steps, []) and max(max(st) for st in steps) <= stride
+    gen = torch.Generator().manual_seed(C)
+    rows = torch.randn(nrows, D, generator=gen)
+    rows_d = rows.to(DEV)
+    offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    caps_np = np.array(caps, dtype=np.int64)
+    state = [torch.full((C, 5), -1, dtype=torch.int64, device=DEV) for _ in range(2)]
+    store = [torch.zeros((int(offs[-1]), D), device=DEV) for _ in range(2)]
+    H.call("u2pl_bank_init", state[0], C, caps_np.ctypes.data)
+    H.call("u2pl_bank_init_wide", state[1], C, caps_np.ctypes.data)
+    assert torch.equal(state[0], state[1])
+    assert state[0].cpu().numpy().tolist() == [[int(offs[c]), caps[c], 0, 0, 0] for c in range(C)]
+    mirror = H.DeviceMemoryBank(C, caps, feat_dim=D, device="cpu")           # host bookkeeping only
+    fifo = [torch.zeros(0, D) for _ in caps]
+    list_off = torch.arange(C, dtype=torch.int64, device=DEV) * stride
+    row_start = torch.arange(C, dtype=torch.int64) * 3 + 5
+    seen = set()
+    for step, cnts in enumerate(steps + [[(c + 2) % 4 for c in range(C)]]):
+        for c in range(C):      # what this count exercises, from the mirror's ring position before it
+            tail = (mirror.head[c] + mirror.length[c]) % caps[c]
+            seen |= {"zero"} if cnts[c] == 0 else {"cap"} if cnts[c] == caps[c] else {"over"} if cnts[c] > caps[c] else set()
+            seen |= {"wrap"} if 0 < cnts[c] < caps[c] and tail + cnts[c] > caps[c] else set()
+        cnt_d = torch.tensor(cnts, dtype=torch.int32, device=DEV)
+        if step < 3:
+            idx = torch.randint(0, nrows, (C, stride), generator=gen, dtype=torch.int32)
+            src = [idx[c, :cnts[c]].long() for c in range(C)]
+            idx_d = idx.to(DEV)
+            H.call("u2pl_bank_enqueue_f32", state[0], store[0], D, rows_d, D, idx_d, stride, None, cnt_d, C)
+            H.call("u2pl_bank_enqueue_wide_f32", state[1], store[1], D, rows_d, D, idx_d.reshape(-1), list_off, None, cnt_d, C)
+        else:
+            src = [int(row_start[c]) + torch.arange(cnts[c]) for c in range(C)]
+            H.call("u2pl_bank_enqueue_f32", state[0], store[0], D, rows_d, D, None, 0, row_start.to(DEV), cnt_d, C)
+            H.call("u2pl_bank_enqueue_wide_f32", state[1], store[1], D, rows_d, D, None, None, row_start.to(DEV), cnt_d, C)
+        mirror.mirror_counts(cnts)
+        assert torch.equal(state[0], state[1]), step
+        assert torch.equal(store[0].view(torch.int32), store[1].view(torch.int32)), step
+        st = state[0].cpu().numpy()
+        assert st[:, 2].tolist() == mirror.head and st[:, 3].tolist() == mirror.length and st[:, 4].tolist() == mirror.ptr
+        got = store[0].cpu()
+        for c in range(C):
+            fifo[c] = torch.cat((fifo[c], rows[src[c]]))[-caps[c]:]
+            ring = (mirror.head[c] + np.arange(mirror.length[c])) % caps[c] + int(offs[c])
+            assert torch.equal(got[ring], fifo[c]), (step, c)
+    assert seen >= ({"zero", "cap", "over"} | ({"wrap"} if C > 3 else set())), seen
 
 
 # ------------------------------------------------------------------ 4. unchanged calls at C <= 32

@@ -30,6 +30,13 @@ def planes_from_onehot(oh):
     return out
 
 
+def label_planes(label_l, label_u, C, s):
+    """the label bits of the concatenated low-res batch as word planes (W,2B,s,s): label_onehot's slot-0 quirk on the
+    full-size labels, then the legacy-nearest down-sampling (oracle/restate.py)"""
+    oh = [R.nearest_down(R.label_onehot_quirk(lab, C), s, s) for lab in (label_l, label_u)]
+    return planes_from_onehot(np.concatenate(oh))
+
+
 def onehot_from_planes(planes, C):
     return np.stack([(planes[c >> 5] >> np.uint32(c & 31)) & np.uint32(1) for c in range(C)], 1).astype(np.int64)
 

@@ -11,6 +11,7 @@
 // Everything here is integer or ordered double-precision arithmetic: the same bits on every run.
 #include <stdint.h>
 #include "common.h"
+#include "class_lists.h"
 #include "u2pl_hip.h"
 
 #define WIDE_MAXC 255
@@ -109,32 +110,6 @@ __global__ __launch_bounds__(256) void k_wide_classify(
     for (int i = t; i < 3 * C; i += PIX) blk[(long)i * nblk + blockIdx.x] = cnt[i];
 }
 
-// exclusive scan over the blocks, one 256-thread block per (kind, class) row of blk; counts[row] = the list length
-__global__ __launch_bounds__(256) void k_wide_scan(unsigned* __restrict__ blk, int nblk, unsigned* __restrict__ counts) {
-    __shared__ unsigned wsum[4];
-    unsigned* row = blk + (long)blockIdx.x * nblk;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    unsigned carry = 0;
-    for (int base = 0; base < nblk; base += 256) {
-        const int b = base + t;
-        const unsigned v = b < nblk ? row[b] : 0;
-        unsigned x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = __shfl_up(x, o, 64);
-            if (lane >= o) x += u;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        unsigned wb = 0;
-        for (int w2 = 0; w2 < wave; ++w2) wb += wsum[w2];
-        const unsigned tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (b < nblk) row[b] = carry + wb + x - v;
-        carry += tot;
-        __syncthreads();
-    }
-    if (t == 0) counts[blockIdx.x] = carry;
-}
 // offsets[kind][c] = first element of list (kind, c) in the flat buffer: the running sum of the 3 C list lengths in
 // (kind, class) order (<= 765 terms: one thread)
 __global__ void k_wide_offsets(const unsigned* __restrict__ counts, int n, long long* __restrict__ offsets) {
@@ -165,7 +140,7 @@ U2PL_API int u2pl_contra_classify_wide(const float* prob, long sn, long sc, long
                     lbits, low_mask, high_mask, N2, num_labeled, C, W, (long)h * w, thr_p, thr_n, low_rank, high_rank,
                     abits, lowbits, nbits, blk, nblk);
     U2PL_LAUNCH_CHECK();
-    U2PL_LAUNCH(k_wide_scan, dim3(3 * C), dim3(256), 0, stream, blk, nblk, counts);
+    U2PL_LAUNCH(k_compact_scan, dim3(3 * C), dim3(256), 0, stream, blk, nblk, counts);
     U2PL_LAUNCH_CHECK();
     U2PL_LAUNCH(k_wide_offsets, dim3(1), dim3(64), 0, stream, counts, 3 * C, offsets);
     U2PL_LAUNCH_CHECK();
@@ -177,11 +152,6 @@ U2PL_API int u2pl_contra_classify_wide(const float* prob, long sn, long sc, long
 // the low-valid list is what the prototypes sum over).  A block's offset inside list (kind, c) is the scanned per-block
 // count, inside the block the waves' ballots: integer only, row-major pixel order.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned wide_wave_or(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return __builtin_amdgcn_readfirstlane(v);
-}
 __global__ __launch_bounds__(256) void k_wide_write(const unsigned* __restrict__ b0, const unsigned* __restrict__ b1,
                                                     const unsigned* __restrict__ b2, long P, const unsigned* __restrict__ blk,
                                                     int nblk, int C, const long long* __restrict__ offsets,
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(256) void k_wide_write(const unsigned* __restrict__
     unsigned pres[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        pres[k] = wide_wave_or(v[k]);
+        pres[k] = wave_or_uniform(v[k]);
         for (unsigned x = pres[k]; x; x &= x - 1u) {
             const int c = __ffs(x) - 1;
             const unsigned long long m = __ballot((v[k] >> c) & 1u);
@@ -218,7 +188,7 @@ __global__ __launch_bounds__(256) void k_wide_write(const unsigned* __restrict__
         }
     }
     __syncthreads();
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const unsigned long long lt = lanemask_lt();
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         for (unsigned x = pres[k]; x; x &= x - 1u) {
@@ -281,74 +251,14 @@ U2PL_API int u2pl_class_prototypes_wide(const float* rows, long ld, int D, const
     return 0;
 }
 
-// ---------------------------------------------------------------------------
-// The device-resident bank (contrast.hip, u2pl_bank_*) for up to 255 classes: same state layout (int64 [C][5] = ring
-// offset, cap, head, len, ptr) and the ring rules of dequeue_and_enqueue (utils.py:27-47); class c's new rows are
-// rows[idx[list_off[c] + j]], j < counts_dev[c] (a flat list buffer), or rows[row_start_dev[c] + j] when idx is NULL.
-// ---------------------------------------------------------------------------
-struct WideBankCaps { long long cap[WIDE_MAXC]; };
-__global__ void k_wide_bank_init(long long* __restrict__ state, int C, WideBankCaps caps) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        long long off = 0;
-        for (int c = 0; c < C; ++c) {
-            state[5 * c + 0] = off; state[5 * c + 1] = caps.cap[c]; state[5 * c + 2] = 0; state[5 * c + 3] = 0; state[5 * c + 4] = 0;
-            off += caps.cap[c];
-        }
-    }
-}
+// The device-resident bank (class_lists.h) for up to 255 classes, lists in the flat buffer: class c's list starts at
+// idx + list_off_dev[c].
 U2PL_API int u2pl_bank_init_wide(long long* state, int C, const long long* caps_host, hipStream_t stream) {
-    if (C <= 0 || C > WIDE_MAXC || !state || !caps_host) return U2PL_EINVAL;
-    WideBankCaps caps = {};
-    for (int c = 0; c < C; ++c) {
-        if (caps_host[c] <= 0) return U2PL_EINVAL;
-        caps.cap[c] = caps_host[c];
-    }
-    U2PL_LAUNCH(k_wide_bank_init, dim3(1), dim3(64), 0, stream, state, C, caps);
-    U2PL_LAUNCH_CHECK();
-    return 0;
-}
-__global__ void k_wide_bank_enqueue(const long long* __restrict__ state, float* __restrict__ storage, int D,
-                                    const float* __restrict__ rows, long ld, const int* __restrict__ idx,
-                                    const long long* __restrict__ list_off, const long long* __restrict__ row_start,
-                                    const unsigned* __restrict__ counts) {
-    const int c = blockIdx.y;
-    const long n_new = counts[c];
-    if (n_new <= 0) return;
-    const long off = state[5 * c + 0], cap = state[5 * c + 1], head = state[5 * c + 2], len = state[5 * c + 3];
-    const long tail = (head + len) % cap;
-    const long skip = n_new > cap ? n_new - cap : 0;       // more new rows than slots: only the last `cap` are kept
-    const int D4 = D >> 2;
-    const long total = (n_new - skip) * D4;
-    const int* list = idx ? idx + list_off[c] : nullptr;
-    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const long j = skip + t / D4;
-        const int dd = (int)(t % D4);
-        const long src = list ? (long)list[j] : (row_start ? row_start[c] : 0) + j;
-        long slot = tail + j;
-        slot = slot >= cap ? slot % cap : slot;
-        ((float4*)storage)[(off + slot) * D4 + dd] = *(const float4*)(rows + src * ld + 4 * dd);
-    }
-}
-__global__ void k_wide_bank_advance(long long* __restrict__ state, const unsigned* __restrict__ counts, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const long n = counts[c];
-    const long cap = state[5 * c + 1], head = state[5 * c + 2], len = state[5 * c + 3], ptr = state[5 * c + 4];
-    const long tail = (head + len) % cap;
-    const long nl = len + n < cap ? len + n : cap;
-    const long new_tail = (tail + n) % cap;
-    state[5 * c + 3] = nl;
-    state[5 * c + 2] = ((new_tail - nl) % cap + cap) % cap;
-    state[5 * c + 4] = nl >= cap ? cap : (ptr + n) % cap;
+    return bank_init(state, C, WIDE_MAXC, caps_host, stream);
 }
 U2PL_API int u2pl_bank_enqueue_wide_f32(long long* state, float* storage, int D, const float* rows, long ld, const int* idx,
                                         const long long* list_off_dev, const long long* row_start_dev,
                                         const unsigned* counts_dev, int C, hipStream_t stream) {
     if (D % 4 || C <= 0 || C > WIDE_MAXC || !state || !storage || !rows || !counts_dev || (idx && !list_off_dev)) return U2PL_EINVAL;
-    U2PL_LAUNCH(k_wide_bank_enqueue, dim3(64, C), dim3(256), 0, stream, state, storage, D, rows, ld, idx, list_off_dev,
-                row_start_dev, counts_dev);
-    U2PL_LAUNCH_CHECK();
-    U2PL_LAUNCH(k_wide_bank_advance, dim3(1), dim3(256), 0, stream, state, counts_dev, C);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return bank_enqueue(state, storage, D, rows, ld, idx, 0, list_off_dev, row_start_dev, counts_dev, C, 64, 256, stream);
 }

@@ -486,307 +486,211 @@ U2PL_API int u2pl_apply_drop_i64(const float* entropy, const unsigned* thr_bits,
 // a12/a13: threshold masks + legacy-nearest down-sampling + label multi-hot
 // bits with the label_onehot batch-slot-0 quirk (utils.py:50-59, Q0), for the
 // concatenated batch [labeled B | unlabeled B] at (h,w).
-//   low_mask/high_mask : float (2B,1,h,w)      lbits : u32 (2B,h,w)
+//   low_mask/high_mask : float (2B,1,h,w)
+//   lbits              : u32 (2B,h,w), one word per pixel (up to 32 classes), or WIDE: word planes u32 [NW][2B*h*w],
+//                        NW = ceil(C / 32), plane g = classes 32 g .. 32 g + 31 (up to 255; csrc/contrast_wide.hip)
+// One body for both layouts; with WIDE == false the plane loop and the plane stride are compiled out.  The ONLY
+// difference in rule between the two instantiations: the one-word form sets a bit for any label below 32, whatever C is
+// (C and NW are unused there; the entry points pass 32 and 1); the WIDE form sets no bit for a label >= C.
 // ---------------------------------------------------------------------------
-__global__ void k_reliability_masks(const float* __restrict__ ent, const unsigned* __restrict__ thr_lo_bits,
-                                    const unsigned* __restrict__ thr_hi_bits,
-                                    const long long* __restrict__ label_l,
-                                    const long long* __restrict__ label_u, int ignore, int B, int H, int W,
-                                    int h, int w, float ny, float nx, int neg_high,
-                                    float* __restrict__ low_mask, float* __restrict__ high_mask,
-                                    unsigned* __restrict__ lbits) {
-    const float tlo = __uint_as_float(*thr_lo_bits), thi = __uint_as_float(*thr_hi_bits);
-    long total = (long)2 * B * h * w;
-    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total;
-         p += (long)gridDim.x * blockDim.x) {
-        int x = (int)(p % w);
-        long t = p / w;
-        int y = (int)(t % h);
-        int n = (int)(t / h);
-        long src = (long)nearest_src(y, ny, H) * W + nearest_src(x, nx, W);
-        const long HW = (long)H * W;
-        float lo, hi;
-        const long long* lab = n < B ? label_l : label_u;
-        int b = n < B ? n : n - B;
-        if (n < B) {
-            lo = hi = lab[b * HW + src] != ignore ? 1.f : 0.f;
-        } else {
-            float e = ent[b * HW + src];  // NaN where label_u == ignore -> both false
-            lo = e <= tlo ? 1.f : 0.f;
-            hi = neg_high ? (e >= thi ? 1.f : 0.f) : 1.f;
-        }
-        low_mask[p] = lo;
-        high_mask[p] = hi;
-        unsigned bits = 0;
-        if (b == 0 && lab[src] != ignore) {  // slot 0: union over the half-batch, zeroed on own ignore
-            for (int bb = 0; bb < B; ++bb) {
-                long long l = lab[bb * HW + src];
-                bits |= 1u << (l == ignore ? 0 : (int)l);
-            }
-        }
-        lbits[p] = bits;
+// low-resolution pixel q of nlow = 2 B h w: masks, and the label bits (Q0: slot 0 holds the union over the half batch, an
+// ignored label of another sample counts as class 0, zeroed on the pixel's own ignore; the other slots hold nothing)
+template <bool WIDE>
+__device__ __forceinline__ void reliability_low_pixel(long q, long nlow, const float* __restrict__ ent, float tlo, float thi,
+                                                      const long long* __restrict__ label_l,
+                                                      const long long* __restrict__ label_u, int ignore, int B, int H, int W,
+                                                      int h, int w, float ny, float nx, int neg_high, int C, int NW,
+                                                      float* __restrict__ low_mask, float* __restrict__ high_mask,
+                                                      unsigned* __restrict__ lbits) {
+    const long HW = (long)H * W;
+    const int x = (int)(q % w);
+    const long t = q / w;
+    const int y = (int)(t % h), n = (int)(t / h);
+    const long src = (long)nearest_src(y, ny, H) * W + nearest_src(x, nx, W);
+    const long long* lab = n < B ? label_l : label_u;
+    const int b = n < B ? n : n - B;
+    float lo, hi;
+    if (n < B) lo = hi = lab[b * HW + src] != ignore ? 1.f : 0.f;
+    else {
+        const float e = ent[b * HW + src];   // NaN where label_u == ignore -> both false
+        lo = e <= tlo ? 1.f : 0.f;
+        hi = neg_high ? (e >= thi ? 1.f : 0.f) : 1.f;
     }
-}
-
-// One launch for the whole tail of the split: unsup target overwrite (loss_helper.py:41-44) on the
-// full-res grid AND the low-res masks / class bits (train_semi.py:408-465).  Thresholds are read from
-// the select workspace: thr_bits[0] = drop, [1] = low, [2] = high.
-__global__ void k_reliability_apply(const float* __restrict__ ent, const unsigned* __restrict__ thr_bits,
-                                    const long long* __restrict__ label_l, const long long* __restrict__ label_u,
-                                    int ignore, int B, int H, int W, int h, int w, float ny, float nx, int neg_high,
-                                    long long* __restrict__ target_u, unsigned* __restrict__ nkept,
-                                    float* __restrict__ low_mask, float* __restrict__ high_mask,
-                                    unsigned* __restrict__ lbits) {
-    const float tdrop = __uint_as_float(thr_bits[0]), tlo = __uint_as_float(thr_bits[1]),
-                thi = __uint_as_float(thr_bits[2]);
-    const long HW = (long)H * W, nfull = (long)B * HW, nlow = (long)2 * B * h * w;
-    unsigned cnt = 0;
-    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < nfull + nlow; p += (long)gridDim.x * blockDim.x) {
-        if (p < nfull) {
-            long long t = label_u[p];
-            if (ent[p] >= tdrop && t != ignore) t = ignore;
-            target_u[p] = t;
-            cnt += t != ignore;
-        } else {
-            const long q = p - nfull;
-            const int x = (int)(q % w);
-            const long t = q / w;
-            const int y = (int)(t % h), n = (int)(t / h);
-            const long src = (long)nearest_src(y, ny, H) * W + nearest_src(x, nx, W);
-            const long long* lab = n < B ? label_l : label_u;
-            const int b = n < B ? n : n - B;
-            float lo, hi;
-            if (n < B) lo = hi = lab[b * HW + src] != ignore ? 1.f : 0.f;
-            else {
-                const float e = ent[b * HW + src];
-                lo = e <= tlo ? 1.f : 0.f;
-                hi = neg_high ? (e >= thi ? 1.f : 0.f) : 1.f;
-            }
-            low_mask[q] = lo;
-            high_mask[q] = hi;
-            unsigned bits = 0;
-            if (b == 0 && lab[src] != ignore)
-                for (int bb = 0; bb < B; ++bb) {
-                    const long long l = lab[bb * HW + src];
-                    bits |= 1u << (l == ignore ? 0 : (int)l);
-                }
-            lbits[q] = bits;
-        }
-    }
-    block_count_flush(cnt, nkept);
-}
-U2PL_API int u2pl_reliability_apply(const float* entropy, const unsigned* thr_bits, const long long* label_l,
-                                    const long long* label_u, int ignore, int B, int H, int W, int h, int w,
-                                    int negative_high_entropy, long long* target_u, unsigned* nkept, float* low_mask,
-                                    float* high_mask, unsigned* lbits, hipStream_t stream) {
-    const long total = (long)B * H * W + (long)2 * B * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_reliability_apply, dim3(grid_for(total, 256, 1024)), dim3(256), 0, stream, entropy, thr_bits, label_l,
-                       label_u, ignore, B, H, W, h, w, (float)H / (float)h, (float)W / (float)w, negative_high_entropy,
-                       target_u, nkept, low_mask, high_mask, lbits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
-}
-
-U2PL_API int u2pl_reliability_masks(const float* entropy, const unsigned* thr_lo_bits,
-                                    const unsigned* thr_hi_bits, const long long* label_l,
-                                    const long long* label_u, int ignore, int B, int H, int W, int h, int w,
-                                    int negative_high_entropy, float* low_mask, float* high_mask,
-                                    unsigned* lbits, hipStream_t stream) {
-    long total = (long)2 * B * h * w;
-    if (total <= 0) return 0;
-    float ny = (float)H / (float)h, nx = (float)W / (float)w;
-    U2PL_LAUNCH(k_reliability_masks, dim3(grid_for(total, 256)), dim3(256), 0, stream, entropy,
-                       thr_lo_bits, thr_hi_bits, label_l, label_u, ignore, B, H, W, h, w, ny, nx,
-                       negative_high_entropy, low_mask, high_mask, lbits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
-}
-
-// bits <-> (N,C,h,w) int64 multi-hot (API parity with compute_contra_memobank_loss inputs)
-__global__ void k_pack_bits(const long long* __restrict__ oh, int N, int C, long hw, unsigned* __restrict__ bits) {
-    long total = (long)N * hw;
-    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-        long n = p / hw, q = p % hw;
-        unsigned b = 0;
-        for (int c = 0; c < C; ++c) b |= (oh[(n * C + c) * hw + q] != 0 ? 1u : 0u) << c;
-        bits[p] = b;
-    }
-}
-__global__ void k_unpack_bits(const unsigned* __restrict__ bits, int N, int C, long hw, long long* __restrict__ oh) {
-    long total = (long)N * C * hw;
-    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-        long q = p % hw;
-        long t = p / hw;
-        int c = (int)(t % C);
-        long n = t / C;
-        oh[p] = (bits[n * hw + q] >> c) & 1u;
-    }
-}
-U2PL_API int u2pl_pack_class_bits(const long long* onehot, int N, int C, int h, int w, unsigned* bits,
-                                  hipStream_t stream) {
-    if (C > 32) return U2PL_EINVAL;
-    long total = (long)N * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_pack_bits, dim3(grid_for(total, 256)), dim3(256), 0, stream, onehot, N, C, (long)h * w, bits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
-}
-U2PL_API int u2pl_unpack_class_bits(const unsigned* bits, int N, int C, int h, int w, long long* onehot,
-                                    hipStream_t stream) {
-    long total = (long)N * C * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_unpack_bits, dim3(grid_for(total, 256)), dim3(256), 0, stream, bits, N, C, (long)h * w, onehot);
-    U2PL_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// The same three producers for MORE THAN 32 CLASSES (up to 255; csrc/contrast_wide.hip consumes them): the class bits are
-// WORD PLANES, lbits u32 [W][2B*h*w] with W = ceil(C / 32), plane g = classes 32 g .. 32 g + 31.  Masks, the legacy-nearest
-// down-sampling and the label_onehot slot-0 quirk (Q0: union over the half batch, an ignored label of another sample counts
-// as class 0, zeroed on the pixel's own ignore) are those of the narrow forms above.  A label >= C sets no bit.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void wide_label_bits(const long long* __restrict__ lab, long src, long HW, int B, int b, int ignore,
-                                                int C, int W, long plane, long q, unsigned* __restrict__ lbits) {
+    low_mask[q] = lo;
+    high_mask[q] = hi;
     const bool on = b == 0 && lab[src] != ignore;
-    for (int g = 0; g < W; ++g) {
+    for (int g = 0; g < (WIDE ? NW : 1); ++g) {
         unsigned bits = 0;
         if (on)
             for (int bb = 0; bb < B; ++bb) {
                 const long long l0 = lab[bb * HW + src];
                 const long long l = l0 == ignore ? 0 : l0;
-                if (l >= 32 * g && l < 32 * g + 32 && l < C) bits |= 1u << (int)(l - 32 * g);
+                if (!WIDE) bits |= 1u << (int)l;
+                else if (l >= 32 * g && l < 32 * g + 32 && l < C) bits |= 1u << (int)(l - 32 * g);
             }
-        lbits[g * plane + q] = bits;
+        lbits[(WIDE ? g * nlow : 0) + q] = bits;
     }
 }
-__global__ void k_reliability_masks_wide(const float* __restrict__ ent, const unsigned* __restrict__ thr_lo_bits,
-                                         const unsigned* __restrict__ thr_hi_bits, const long long* __restrict__ label_l,
-                                         const long long* __restrict__ label_u, int ignore, int B, int H, int W, int h, int w,
-                                         float ny, float nx, int neg_high, int C, int NW, float* __restrict__ low_mask,
-                                         float* __restrict__ high_mask, unsigned* __restrict__ lbits) {
+// full-resolution pixel p: unsup target overwrite (loss_helper.py:41-44); returns 1 for a kept pixel
+__device__ __forceinline__ unsigned reliability_target_pixel(long p, const float* __restrict__ ent, float tdrop,
+                                                             const long long* __restrict__ label_u, int ignore,
+                                                             long long* __restrict__ target_u) {
+    long long t = label_u[p];
+    if (ent[p] >= tdrop && t != ignore) t = ignore;
+    target_u[p] = t;
+    return t != ignore;
+}
+
+template <bool WIDE>
+__global__ void k_reliability_masks(const float* __restrict__ ent, const unsigned* __restrict__ thr_lo_bits,
+                                    const unsigned* __restrict__ thr_hi_bits, const long long* __restrict__ label_l,
+                                    const long long* __restrict__ label_u, int ignore, int B, int H, int W, int h, int w,
+                                    float ny, float nx, int neg_high, int C, int NW, float* __restrict__ low_mask,
+                                    float* __restrict__ high_mask, unsigned* __restrict__ lbits) {
     const float tlo = __uint_as_float(*thr_lo_bits), thi = __uint_as_float(*thr_hi_bits);
-    const long total = (long)2 * B * h * w, HW = (long)H * W;
-    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(p % w);
-        const long t = p / w;
-        const int y = (int)(t % h), n = (int)(t / h);
-        const long src = (long)nearest_src(y, ny, H) * W + nearest_src(x, nx, W);
-        const long long* lab = n < B ? label_l : label_u;
-        const int b = n < B ? n : n - B;
-        float lo, hi;
-        if (n < B) lo = hi = lab[b * HW + src] != ignore ? 1.f : 0.f;
-        else {
-            const float e = ent[b * HW + src];   // NaN where label_u == ignore -> both false
-            lo = e <= tlo ? 1.f : 0.f;
-            hi = neg_high ? (e >= thi ? 1.f : 0.f) : 1.f;
-        }
-        low_mask[p] = lo;
-        high_mask[p] = hi;
-        wide_label_bits(lab, src, HW, B, b, ignore, C, NW, total, p, lbits);
-    }
+    const long total = (long)2 * B * h * w;
+    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x)
+        reliability_low_pixel<WIDE>(p, total, ent, tlo, thi, label_l, label_u, ignore, B, H, W, h, w, ny, nx, neg_high, C, NW,
+                                    low_mask, high_mask, lbits);
 }
-__global__ void k_reliability_apply_wide(const float* __restrict__ ent, const unsigned* __restrict__ thr_bits,
-                                         const long long* __restrict__ label_l, const long long* __restrict__ label_u,
-                                         int ignore, int B, int H, int W, int h, int w, float ny, float nx, int neg_high, int C,
-                                         int NW, long long* __restrict__ target_u, unsigned* __restrict__ nkept,
-                                         float* __restrict__ low_mask, float* __restrict__ high_mask,
-                                         unsigned* __restrict__ lbits) {
+
+// One launch for the whole tail of the split: unsup target overwrite on the full-res grid AND the low-res masks / class
+// bits (train_semi.py:408-465).  Thresholds are read from the select workspace: thr_bits[0] = drop, [1] = low, [2] = high.
+template <bool WIDE>
+__global__ void k_reliability_apply(const float* __restrict__ ent, const unsigned* __restrict__ thr_bits,
+                                    const long long* __restrict__ label_l, const long long* __restrict__ label_u,
+                                    int ignore, int B, int H, int W, int h, int w, float ny, float nx, int neg_high, int C,
+                                    int NW, long long* __restrict__ target_u, unsigned* __restrict__ nkept,
+                                    float* __restrict__ low_mask, float* __restrict__ high_mask,
+                                    unsigned* __restrict__ lbits) {
     const float tdrop = __uint_as_float(thr_bits[0]), tlo = __uint_as_float(thr_bits[1]), thi = __uint_as_float(thr_bits[2]);
-    const long HW = (long)H * W, nfull = (long)B * HW, nlow = (long)2 * B * h * w;
+    const long nfull = (long)B * H * W, nlow = (long)2 * B * h * w;
     unsigned cnt = 0;
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < nfull + nlow; p += (long)gridDim.x * blockDim.x) {
-        if (p < nfull) {
-            long long t = label_u[p];
-            if (ent[p] >= tdrop && t != ignore) t = ignore;
-            target_u[p] = t;
-            cnt += t != ignore;
-        } else {
-            const long q = p - nfull;
-            const int x = (int)(q % w);
-            const long t = q / w;
-            const int y = (int)(t % h), n = (int)(t / h);
-            const long src = (long)nearest_src(y, ny, H) * W + nearest_src(x, nx, W);
-            const long long* lab = n < B ? label_l : label_u;
-            const int b = n < B ? n : n - B;
-            float lo, hi;
-            if (n < B) lo = hi = lab[b * HW + src] != ignore ? 1.f : 0.f;
-            else {
-                const float e = ent[b * HW + src];
-                lo = e <= tlo ? 1.f : 0.f;
-                hi = neg_high ? (e >= thi ? 1.f : 0.f) : 1.f;
-            }
-            low_mask[q] = lo;
-            high_mask[q] = hi;
-            wide_label_bits(lab, src, HW, B, b, ignore, C, NW, nlow, q, lbits);
-        }
+        if (p < nfull) cnt += reliability_target_pixel(p, ent, tdrop, label_u, ignore, target_u);
+        else
+            reliability_low_pixel<WIDE>(p - nfull, nlow, ent, tlo, thi, label_l, label_u, ignore, B, H, W, h, w, ny, nx,
+                                        neg_high, C, NW, low_mask, high_mask, lbits);
     }
     block_count_flush(cnt, nkept);
+}
+
+template <bool WIDE>
+static int reliability_apply(const float* entropy, const unsigned* thr_bits, const long long* label_l,
+                             const long long* label_u, int ignore, int B, int H, int W, int h, int w, int neg_high, int C,
+                             long long* target_u, unsigned* nkept, float* low_mask, float* high_mask, unsigned* lbits,
+                             hipStream_t stream) {
+    const long total = (long)B * H * W + (long)2 * B * h * w;
+    if (total <= 0) return 0;
+    U2PL_LAUNCH(k_reliability_apply<WIDE>, dim3(grid_for(total, 256, 1024)), dim3(256), 0, stream, entropy, thr_bits, label_l,
+                label_u, ignore, B, H, W, h, w, (float)H / (float)h, (float)W / (float)w, neg_high, C, (C + 31) / 32,
+                target_u, nkept, low_mask, high_mask, lbits);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+template <bool WIDE>
+static int reliability_masks(const float* entropy, const unsigned* thr_lo_bits, const unsigned* thr_hi_bits,
+                             const long long* label_l, const long long* label_u, int ignore, int B, int H, int W, int h, int w,
+                             int neg_high, int C, float* low_mask, float* high_mask, unsigned* lbits, hipStream_t stream) {
+    const long total = (long)2 * B * h * w;
+    if (total <= 0) return 0;
+    U2PL_LAUNCH(k_reliability_masks<WIDE>, dim3(grid_for(total, 256)), dim3(256), 0, stream, entropy, thr_lo_bits,
+                thr_hi_bits, label_l, label_u, ignore, B, H, W, h, w, (float)H / (float)h, (float)W / (float)w, neg_high, C,
+                (C + 31) / 32, low_mask, high_mask, lbits);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+U2PL_API int u2pl_reliability_apply(const float* entropy, const unsigned* thr_bits, const long long* label_l,
+                                    const long long* label_u, int ignore, int B, int H, int W, int h, int w,
+                                    int negative_high_entropy, long long* target_u, unsigned* nkept, float* low_mask,
+                                    float* high_mask, unsigned* lbits, hipStream_t stream) {
+    return reliability_apply<false>(entropy, thr_bits, label_l, label_u, ignore, B, H, W, h, w, negative_high_entropy, 32,
+                                    target_u, nkept, low_mask, high_mask, lbits, stream);
+}
+U2PL_API int u2pl_reliability_masks(const float* entropy, const unsigned* thr_lo_bits,
+                                    const unsigned* thr_hi_bits, const long long* label_l,
+                                    const long long* label_u, int ignore, int B, int H, int W, int h, int w,
+                                    int negative_high_entropy, float* low_mask, float* high_mask,
+                                    unsigned* lbits, hipStream_t stream) {
+    return reliability_masks<false>(entropy, thr_lo_bits, thr_hi_bits, label_l, label_u, ignore, B, H, W, h, w,
+                                    negative_high_entropy, 32, low_mask, high_mask, lbits, stream);
 }
 U2PL_API int u2pl_reliability_apply_wide(const float* entropy, const unsigned* thr_bits, const long long* label_l,
                                          const long long* label_u, int ignore, int B, int H, int W, int h, int w,
                                          int negative_high_entropy, int C, long long* target_u, unsigned* nkept,
                                          float* low_mask, float* high_mask, unsigned* lbits, hipStream_t stream) {
     if (C <= 0 || C > 255) return U2PL_EINVAL;
-    const long total = (long)B * H * W + (long)2 * B * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_reliability_apply_wide, dim3(grid_for(total, 256, 1024)), dim3(256), 0, stream, entropy, thr_bits, label_l,
-                label_u, ignore, B, H, W, h, w, (float)H / (float)h, (float)W / (float)w, negative_high_entropy, C, (C + 31) / 32,
-                target_u, nkept, low_mask, high_mask, lbits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return reliability_apply<true>(entropy, thr_bits, label_l, label_u, ignore, B, H, W, h, w, negative_high_entropy, C,
+                                   target_u, nkept, low_mask, high_mask, lbits, stream);
 }
 U2PL_API int u2pl_reliability_masks_wide(const float* entropy, const unsigned* thr_lo_bits, const unsigned* thr_hi_bits,
                                          const long long* label_l, const long long* label_u, int ignore, int B, int H, int W,
                                          int h, int w, int negative_high_entropy, int C, float* low_mask, float* high_mask,
                                          unsigned* lbits, hipStream_t stream) {
     if (C <= 0 || C > 255) return U2PL_EINVAL;
-    const long total = (long)2 * B * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_reliability_masks_wide, dim3(grid_for(total, 256)), dim3(256), 0, stream, entropy, thr_lo_bits, thr_hi_bits,
-                label_l, label_u, ignore, B, H, W, h, w, (float)H / (float)h, (float)W / (float)w, negative_high_entropy, C,
-                (C + 31) / 32, low_mask, high_mask, lbits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return reliability_masks<true>(entropy, thr_lo_bits, thr_hi_bits, label_l, label_u, ignore, B, H, W, h, w,
+                                   negative_high_entropy, C, low_mask, high_mask, lbits, stream);
 }
-// bit planes [W][N*h*w] <-> (N,C,h,w) int64 multi-hot
-__global__ void k_pack_bits_wide(const long long* __restrict__ oh, int N, int C, int NW, long hw, unsigned* __restrict__ bits) {
+
+// class bits <-> (N,C,h,w) int64 multi-hot (API parity with compute_contra_memobank_loss inputs): one word per pixel
+// (C <= 32), or WIDE: bit planes [NW][N*h*w].  The one-word form is the one-plane case, its loop and stride compiled out.
+template <bool WIDE>
+__global__ void k_pack_bits(const long long* __restrict__ oh, int N, int C, int NW, long hw, unsigned* __restrict__ bits) {
     const long total = (long)N * hw;
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const long n = p / hw, q = p % hw;
-        for (int g = 0; g < NW; ++g) {
+        for (int g = 0; g < (WIDE ? NW : 1); ++g) {
+            const int c1 = WIDE ? min(C, 32 * g + 32) : C;
             unsigned b = 0;
-            for (int c = 32 * g; c < C && c < 32 * g + 32; ++c) b |= (oh[(n * C + c) * hw + q] != 0 ? 1u : 0u) << (c - 32 * g);
-            bits[g * total + p] = b;
+            for (int c = 32 * g; c < c1; ++c) b |= (oh[(n * C + c) * hw + q] != 0 ? 1u : 0u) << (c - 32 * g);
+            bits[(WIDE ? g * total : 0) + p] = b;
         }
     }
 }
-__global__ void k_unpack_bits_wide(const unsigned* __restrict__ bits, int N, int C, long hw, long long* __restrict__ oh) {
+template <bool WIDE>
+__global__ void k_unpack_bits(const unsigned* __restrict__ bits, int N, int C, long hw, long long* __restrict__ oh) {
     const long total = (long)N * C * hw, plane = (long)N * hw;
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const long q = p % hw;
         const long t = p / hw;
         const int c = (int)(t % C);
         const long n = t / C;
-        oh[p] = (bits[(c >> 5) * plane + n * hw + q] >> (c & 31)) & 1u;
+        oh[p] = (bits[(WIDE ? (c >> 5) * plane : 0) + n * hw + q] >> (WIDE ? c & 31 : c)) & 1u;
     }
+}
+template <bool WIDE>
+static int pack_class_bits(const long long* onehot, int N, int C, int h, int w, unsigned* bits, hipStream_t stream) {
+    const long total = (long)N * h * w;
+    if (total <= 0) return 0;
+    U2PL_LAUNCH(k_pack_bits<WIDE>, dim3(grid_for(total, 256)), dim3(256), 0, stream, onehot, N, C, (C + 31) / 32, (long)h * w,
+                bits);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+template <bool WIDE>
+static int unpack_class_bits(const unsigned* bits, int N, int C, int h, int w, long long* onehot, hipStream_t stream) {
+    const long total = (long)N * C * h * w;
+    if (total <= 0) return 0;
+    U2PL_LAUNCH(k_unpack_bits<WIDE>, dim3(grid_for(total, 256)), dim3(256), 0, stream, bits, N, C, (long)h * w, onehot);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+U2PL_API int u2pl_pack_class_bits(const long long* onehot, int N, int C, int h, int w, unsigned* bits,
+                                  hipStream_t stream) {
+    if (C > 32) return U2PL_EINVAL;
+    return pack_class_bits<false>(onehot, N, C, h, w, bits, stream);
+}
+U2PL_API int u2pl_unpack_class_bits(const unsigned* bits, int N, int C, int h, int w, long long* onehot,
+                                    hipStream_t stream) {
+    return unpack_class_bits<false>(bits, N, C, h, w, onehot, stream);
 }
 U2PL_API int u2pl_pack_class_bits_wide(const long long* onehot, int N, int C, int h, int w, unsigned* bits,
                                        hipStream_t stream) {
     if (C <= 0 || C > 255) return U2PL_EINVAL;
-    const long total = (long)N * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_pack_bits_wide, dim3(grid_for(total, 256)), dim3(256), 0, stream, onehot, N, C, (C + 31) / 32, (long)h * w, bits);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return pack_class_bits<true>(onehot, N, C, h, w, bits, stream);
 }
 U2PL_API int u2pl_unpack_class_bits_wide(const unsigned* bits, int N, int C, int h, int w, long long* onehot,
                                          hipStream_t stream) {
     if (C <= 0 || C > 255) return U2PL_EINVAL;
-    const long total = (long)N * C * h * w;
-    if (total <= 0) return 0;
-    U2PL_LAUNCH(k_unpack_bits_wide, dim3(grid_for(total, 256)), dim3(256), 0, stream, bits, N, C, (long)h * w, onehot);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return unpack_class_bits<true>(bits, N, C, h, w, onehot, stream);
 }

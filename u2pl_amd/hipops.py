@@ -31,6 +31,19 @@ def check_num_classes(C, what="num_classes"):
         raise ValueError(f"{what} = {int(C)}: expected a positive class count")
 
 
+def _class_bits(num_classes, pixels, dev, wide=None):
+    """the class-bit tensor of `pixels` = (N, h, w) and what selects its C symbols -> (bits, suffix, extra arguments):
+    one int32 word per pixel, "" and (); or -- wide: num_classes > 32 unless the caller forces it -- word planes
+    (W, N, h, w), "_wide" and (num_classes,), the class count the *_wide reliability entry points take"""
+    if wide is None:
+        wide = num_classes is not None and int(num_classes) > MAXC
+    if not wide:
+        return torch.empty(tuple(pixels), dtype=torch.int32, device=dev), "", ()
+    check_num_classes(num_classes)
+    bits = torch.empty((wide_words(num_classes),) + tuple(pixels), dtype=torch.int32, device=dev)
+    return bits, "_wide", (int(num_classes),)
+
+
 def _f32c(x):
     if x.dtype != torch.float32:
         raise _lib.HipError("expected float32 tensor")
@@ -321,15 +334,9 @@ def reliability_apply(entropy, thr3, label_l, label_u_aug, out_hw, negative_high
     nk = torch.zeros(1, dtype=torch.int32, device=dev)
     low = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
     high = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
-    if num_classes is not None and int(num_classes) > MAXC:
-        check_num_classes(num_classes)
-        lbits = torch.empty((wide_words(num_classes), 2 * B, h, w), dtype=torch.int32, device=dev)
-        call("u2pl_reliability_apply_wide", entropy, thr3, label_l.contiguous(), label_u_aug.contiguous(), ignore, B, H, W, h,
-             w, int(bool(negative_high_entropy)), int(num_classes), target, nk, low, high, lbits)
-        return target, nk, low, high, lbits
-    lbits = torch.empty((2 * B, h, w), dtype=torch.int32, device=dev)
-    call("u2pl_reliability_apply", entropy, thr3, label_l.contiguous(), label_u_aug.contiguous(), ignore, B, H, W, h, w,
-         int(bool(negative_high_entropy)), target, nk, low, high, lbits)
+    lbits, sfx, nc = _class_bits(num_classes, (2 * B, h, w), dev)
+    call("u2pl_reliability_apply" + sfx, entropy, thr3, label_l.contiguous(), label_u_aug.contiguous(), ignore, B, H, W, h, w,
+         int(bool(negative_high_entropy)), *nc, target, nk, low, high, lbits)
     return target, nk, low, high, lbits
 
 
@@ -575,28 +582,17 @@ def reliability_masks(entropy, thr_lo, thr_hi, label_l, label_u_aug, out_hw, neg
     dev = entropy.device
     low = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
     high = torch.empty((2 * B, 1, h, w), dtype=torch.float32, device=dev)
-    if num_classes is not None and int(num_classes) > MAXC:
-        check_num_classes(num_classes)
-        lbits = torch.empty((wide_words(num_classes), 2 * B, h, w), dtype=torch.int32, device=dev)
-        call("u2pl_reliability_masks_wide", entropy, thr_lo, thr_hi, label_l.contiguous(), label_u_aug.contiguous(),
-             ignore, B, H, W, h, w, int(bool(negative_high_entropy)), int(num_classes), low, high, lbits)
-        return low, high, lbits
-    lbits = torch.empty((2 * B, h, w), dtype=torch.int32, device=dev)
-    call("u2pl_reliability_masks", entropy, thr_lo, thr_hi, label_l.contiguous(), label_u_aug.contiguous(),
-         ignore, B, H, W, h, w, int(bool(negative_high_entropy)), low, high, lbits)
+    lbits, sfx, nc = _class_bits(num_classes, (2 * B, h, w), dev)
+    call("u2pl_reliability_masks" + sfx, entropy, thr_lo, thr_hi, label_l.contiguous(), label_u_aug.contiguous(),
+         ignore, B, H, W, h, w, int(bool(negative_high_entropy)), *nc, low, high, lbits)
     return low, high, lbits
 
 
 def pack_class_bits(onehot, wide=None):
     """(N,C,h,w) multi-hot -> class bits (N,h,w) int32; C > 32 (or wide=True, for tests): word planes (W,N,h,w)"""
     N, C, h, w = onehot.shape
-    if C > MAXC if wide is None else wide:
-        check_num_classes(C)
-        bits = torch.empty((wide_words(C), N, h, w), dtype=torch.int32, device=onehot.device)
-        call("u2pl_pack_class_bits_wide", onehot.long().contiguous(), N, C, h, w, bits)
-        return bits
-    bits = torch.empty((N, h, w), dtype=torch.int32, device=onehot.device)
-    call("u2pl_pack_class_bits", onehot.long().contiguous(), N, C, h, w, bits)
+    bits, sfx, _ = _class_bits(C, (N, h, w), onehot.device, wide)
+    call("u2pl_pack_class_bits" + sfx, onehot.long().contiguous(), N, C, h, w, bits)
     return bits
 
 
@@ -656,14 +652,12 @@ class DeviceMemoryBank:
         the host.  list_off (int64 [C] on the device): idx is a flat list buffer and class c's list starts at
         list_off[c] (the wide route; any C up to 255)."""
         self._sync_state()
-        if list_off is not None or self.C > MAXC:
-            if list_off is None:
-                raise _lib.HipError("enqueue_device: more than 32 classes need the flat list layout (list_off)")
-            call("u2pl_bank_enqueue_wide_f32", self.state, self.storage, self.D, rows, ld, idx, list_off, None, counts_dev,
-                 self.C)
-            return
-        call("u2pl_bank_enqueue_f32", self.state, self.storage, self.D, rows, ld, idx, idx_stride, None, counts_dev, self.C)
-        if REPLAY is not None:
+        wide = list_off is not None or self.C > MAXC
+        if wide and list_off is None:
+            raise _lib.HipError("enqueue_device: more than 32 classes need the flat list layout (list_off)")
+        call("u2pl_bank_enqueue_wide_f32" if wide else "u2pl_bank_enqueue_f32", self.state, self.storage, self.D, rows, ld, idx,
+             list_off if wide else idx_stride, None, counts_dev, self.C)
+        if REPLAY is not None and not wide:
             REPLAY["enqueue"] = (rows, ld, idx, idx_stride, counts_dev)
             REPLAY["bank"] = self
 
