@@ -383,11 +383,30 @@ int u2pl_gemm_batched_ws_f32(const float* x, long ldx, long zx, const void* wspl
  *     within ~2^8 of the true maximum keeps fp32-class accuracy; a value BELOW the maximum overflows fp16.
  *   u2pl_conv2d_fwd_bnact_wsh_f32's y_amax: NULL or an amax object for max |y| of the fused output (the next layer's x_amax).
  *   u2pl_weight_split2h_*: planes [K/32][2][Np][32] fp16 + one uint32 per matrix (bit pattern of its max |w|) behind them.
- *     job_scratch: 48 device bytes (the job record of the one-weight call).  The multi call takes the SplitJob table of
- *     u2pl_weight_split3_multi_f32 with out = u2pl_weight_split2h_bytes buffers. */
+ *     job_scratch: 48 device bytes, non-NULL (kept for the ABI; the one-weight call passes its job record by value).  The multi
+ *     call takes the SplitJob table of u2pl_weight_split3_multi_f32 with out = u2pl_weight_split2h_bytes buffers. */
 size_t u2pl_weight_split2h_bytes(int rows, int K, int batch);
 int u2pl_weight_split2h_f32(const float* w, long zw, int rows, int K, int batch, void* out, void* job_scratch, hipStream_t stream);
 int u2pl_weight_split2h_multi_f32(const void* jobs, int njobs, long total, hipStream_t stream);
+/* Every split-fp16 operand of a model rebuilt from the WEIGHTS in at most four launches (clear, maxima of every kind, pieces of
+ * kinds 0 / 1, pieces of kinds 2 / 3; three where a table has no Winograd job): the bytes u2pl_weight_split2h_f32 writes for the same
+ * operand -- for kinds 2 / 3 from the U of u2pl_wino_weight_f32 --, without an fp32 U in memory and with max |w| computed once per
+ * weight.  jobs: DEVICE array of n_flat records of kinds 0 / 1 followed by n_wino records of kinds 2 / 3 (u2pl_weight_rebuild2h_job_bytes()
+ * = 72 bytes each):
+ *   struct { const float* src; unsigned short* out; long seg_begin; long amax_begin; unsigned* amax_dst;
+ *            int rows, Np, K, kind, RS, mt; int mblk_begin, pblk_begin; }
+ *     out: a u2pl_weight_split2h_bytes(rows, K, batch) buffer, batch = 1 (kinds 0 / 1) or (mt + 2)^2; Np = u2pl_weight_split3_pad_rows(rows)
+ *     kind 0: src = [rows][K]; kind 1: src = conv weight [Cout][RS][Cin] read as [rows = Cin][K = RS * Cout].  seg_begin = prefix sum of
+ *       Np * K / 8 (seg_total = the sum).  The jobs of one weight share its maximum: amax_dst = the word behind the planes of the
+ *       weight's FIRST job in the table (out + the plane bytes), amax_begin = prefix sum of rows * K / 4 over first jobs (a further job
+ *       of a weight carries the prefix reached so far: length 0; amax_total = the sum)
+ *     kind 2: src = conv weight [O][3][3][C], planes of U[z][rows = O][K = C]; kind 3: planes of U'[z][rows = C][K = O] (rotated taps);
+ *       mt = 2 or 4; C % 4 == 0.  mblk_begin / pblk_begin = prefix sums of ceil(O * C / 4 / span(1)) / ceil(Np * K / 8 / span(2)) with
+ *       span = u2pl_weight_rebuild2h_span (wino_mblocks / wino_pblocks = the sums). */
+int u2pl_weight_rebuild2h_job_bytes(void);
+int u2pl_weight_rebuild2h_span(int which);
+int u2pl_weight_rebuild2h_f32(const void* jobs, int n_flat, int n_wino, long seg_total, long amax_total, int wino_mblocks,
+                              int wino_pblocks, hipStream_t stream);
 int u2pl_amax_words(void);
 int u2pl_absmax_f32(const float* x, long ld, long M, int C, float* out, int clear, hipStream_t stream);
 /* producers that leave the maximum of what they write (fused: no extra pass): the entry points of the same name without

@@ -201,14 +201,59 @@ def ws_wino(weight, transposed, mt, h=None):
                      dict(how="wino", transposed=int(transposed), mt=mt, O=Cout, C=Cin), h)
 
 
-# ---- all derived operands of a model rebuilt in two launches ----------------------------------------------------
+# ---- all derived operands of a model rebuilt in a handful of launches -----------------------------------------------
 # The lazy path above costs two to four tiny launches per weight and step (~660 per step for student + teacher: transposes,
 # Winograd filter transforms, splits).  After the first step every operand a model uses is known: presplit(params), called
-# by the arena right after its optimizer / EMA kernel, rebuilds ALL stale ones with one u2pl_wino_weight_multi_f32 and one
-# u2pl_weight_split3_multi_f32 launch (job tables on the device, re-uploaded only when the set of operands changes) and
-# stamps them current, so the layer calls of the next step find them valid.  Same bits as the lazy path (tested).
+# by the arena right after its optimizer / EMA kernel, rebuilds ALL stale ones from job tables on the device (re-uploaded only
+# when the set of operands changes) and stamps them current, so the layer calls of the next step find them valid.  Same bits as
+# the lazy path (tested).
+#   fp16 planes (CONV_H, the default): ONE u2pl_weight_rebuild2h_f32 call -- four launches (clear, maxima of every kind, pieces of
+#     the plain / transposed operands, pieces of the Winograd ones; three without Winograd operands).  It reads the weights only:
+#     the Winograd components are recomputed from the nine taps in registers (no fp32 U in memory, no scratch arena, no
+#     transform launch) and max |w| is computed once per weight for its "fh" and "dh" operands.  Job record: _RB_JOB below
+#     mirrors csrc/igemm_ws.hip's RebuildJob.
+#   bf16 planes (U2PL_CONV_H=0): one u2pl_wino_weight_multi_f32 launch into a scratch arena and one u2pl_weight_split3_multi_f32.
 # U2PL_PRESPLIT=0: off.
 PRESPLIT = {"on": os.environ.get("U2PL_PRESPLIT", "1") != "0", "tables": {}}
+_RB_JOB = [("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("amax_begin", "<i8"), ("amax_dst", "<u8"), ("rows", "<i4"), ("Np", "<i4"),
+           ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"), ("mt", "<i4"), ("mblk", "<i4"), ("pblk", "<i4")]
+
+
+def _rebuild2h_table(np, jobs, dev):
+    """jobs: [(weight, cache entry)] of fp16-plane operands -> the device table and the arguments of u2pl_weight_rebuild2h_f32"""
+    flat = [(w, e) for w, e in jobs if e["spec"]["how"] != "wino"]
+    wino = [(w, e) for w, e in jobs if e["spec"]["how"] == "wino"]
+    rj = np.zeros(len(jobs), dtype=np.dtype(_RB_JOB))
+    assert rj.dtype.itemsize == query("u2pl_weight_rebuild2h_job_bytes")
+    mspan, pspan = query("u2pl_weight_rebuild2h_span", 1), query("u2pl_weight_rebuild2h_span", 2)
+    seg = amax = 0
+    first = {}                          # weight -> the word that receives its maximum (behind the planes of its first job)
+    for i, (w, e) in enumerate(flat):
+        sp = e["spec"]
+        Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
+        if sp["batch"] != 1 or Np * (sp["K"] // 8) >= 2 ** 31:
+            raise HipError("presplit: unsupported plain / transposed operand %r" % (sp,))
+        tail = e["buf"].data_ptr() + (sp["K"] // 32) * 2 * Np * 64
+        # (a weight's further operands -- "dh" behind "fh" -- read their scale from the FIRST operand's tail word, which only this
+        # table's maxima launch fills: the operands of a weight must be rebuilt together, in one table; never filter jobs per call)
+        dst = first.setdefault(w.data_ptr(), tail)
+        rj[i] = (w.data_ptr(), e["buf"].data_ptr(), seg, amax, dst, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0,
+                 sp.get("RS", 1), 0, 0, 0)
+        seg += Np * (sp["K"] // 8)
+        if dst == tail:
+            amax += sp["rows"] * sp["K"] // 4
+    mblk = pblk = 0
+    for i, (w, e) in enumerate(wino):
+        sp = e["spec"]
+        Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
+        if sp["C"] % 4 or sp["K"] % 32 or sp["batch"] != (sp["mt"] + 2) ** 2 or sp["O"] * sp["C"] >= 2 ** 31:
+            raise HipError("presplit: unsupported Winograd operand %r" % (sp,))
+        rj[len(flat) + i] = (w.data_ptr(), e["buf"].data_ptr(), 0, 0, 0, sp["rows"], Np, sp["K"], 3 if sp["transposed"] else 2, 9,
+                             sp["mt"], mblk, pblk)
+        mblk += -(-(sp["O"] * sp["C"] // 4) // mspan)
+        pblk += -(-(Np * (sp["K"] // 8)) // pspan)
+    return dict(rj=torch.from_numpy(rj.view(np.uint8).copy()).to(dev), n_flat=len(flat), n_rwino=len(wino), seg_h=seg, amax_h=amax,
+                mblk=mblk, pblk=pblk)
 
 
 def presplit(params, owner=None):
@@ -229,51 +274,53 @@ def presplit(params, owner=None):
     cur = torch.cuda.current_stream()
     for st in {s_ for _, e, _ in todo for s_ in (list(e["readers"]) + [e["stream"]]) if s_ != cur}:
         cur.wait_stream(st)          # nobody reads the old planes any more, the previous build is complete
-    todo.sort(key=lambda t_: bool(t_[1]["spec"].get("h")))           # the bf16-plane jobs first, then the fp16-plane ones
+    # the bf16-plane jobs first, then the fp16-plane ones: plain / transposed, then Winograd (the order of the rebuild's table)
+    todo.sort(key=lambda t_: (bool(t_[1]["spec"].get("h")), t_[1]["spec"]["how"] == "wino"))
     n_plain = sum(1 for _, e, _ in todo if not e["spec"].get("h"))
     key = tuple((w.data_ptr(), e["buf"].data_ptr(), e["spec"]["how"], bool(e["spec"].get("h"))) for w, e, _ in todo)
     tab = PRESPLIT["tables"].get(id(owner))
     if tab is None or tab["key"] != key:
         dev = todo[0][0].device
-        sj = np.zeros(len(todo), dtype=np.dtype([("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("rows", "<i4"), ("Np", "<i4"),
-                                                 ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"), ("batch", "<i4")]))
-        wino = [(w, e) for w, e, _ in todo if e["spec"]["how"] == "wino"]
-        wj = np.zeros(max(len(wino), 1), dtype=np.dtype([("w", "<u8"), ("U", "<u8"), ("begin", "<i8"), ("O", "<i4"), ("C", "<i4"),
-                                                         ("tr", "<i4"), ("mt", "<i4")]))
-        # one scratch arena for the Winograd-domain filters (read by the split launch right behind the transform launch)
-        u_off, acc = {}, 0
-        for w, e in wino:
-            sp = e["spec"]
-            u_off[id(e)] = acc
-            acc += sp["batch"] * sp["rows"] * sp["K"]
-        scratch = torch.empty(max(acc, 1), dtype=torch.float32, device=dev)
-        begin = 0
-        for i, (w, e) in enumerate(wino):
-            sp = e["spec"]
-            wj[i] = (w.data_ptr(), scratch.data_ptr() + 4 * u_off[id(e)], begin, sp["O"], sp["C"], sp["transposed"], sp["mt"])
-            begin += sp["O"] * sp["C"]
-        seg, segs = 0, [0, 0]
-        for i, (w, e, _) in enumerate(todo):
-            sp = e["spec"]
-            if i == n_plain:
-                seg = 0                 # (the fp16-plane jobs form a table of their own: segment numbers restart)
-            Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
-            src = scratch.data_ptr() + 4 * u_off[id(e)] if sp["how"] == "wino" else w.data_ptr()
-            sj[i] = (src, e["buf"].data_ptr(), seg, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0,
-                     sp.get("RS", 1), sp["batch"])
-            seg += sp["batch"] * Np * (sp["K"] // 8)
-            segs[int(i >= n_plain)] = seg
-        sj_dev = torch.from_numpy(sj.view(np.uint8).copy()).to(dev)
-        tab = PRESPLIT["tables"][id(owner)] = dict(
-            key=key, scratch=scratch, n_plain=n_plain, n_h=len(todo) - n_plain, seg=segs[0], seg_h=segs[1], n_wino=len(wino),
-            wino_total=begin, sj=sj_dev, sj_h=sj_dev[n_plain * sj.dtype.itemsize:],
-            wj=torch.from_numpy(wj.view(np.uint8).copy()).to(dev))
+        tab = PRESPLIT["tables"][id(owner)] = dict(key=key, n_plain=n_plain, n_h=len(todo) - n_plain, n_wino=0)
+        if n_plain:
+            plain = todo[:n_plain]
+            sj = np.zeros(n_plain, dtype=np.dtype([("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("rows", "<i4"), ("Np", "<i4"),
+                                                   ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"), ("batch", "<i4")]))
+            wino = [(w, e) for w, e, _ in plain if e["spec"]["how"] == "wino"]
+            wj = np.zeros(max(len(wino), 1), dtype=np.dtype([("w", "<u8"), ("U", "<u8"), ("begin", "<i8"), ("O", "<i4"), ("C", "<i4"),
+                                                             ("tr", "<i4"), ("mt", "<i4")]))
+            # one scratch arena for the Winograd-domain filters (read by the split launch right behind the transform launch)
+            u_off, acc = {}, 0
+            for w, e in wino:
+                sp = e["spec"]
+                u_off[id(e)] = acc
+                acc += sp["batch"] * sp["rows"] * sp["K"]
+            scratch = torch.empty(acc, dtype=torch.float32, device=dev) if acc else None
+            begin = 0
+            for i, (w, e) in enumerate(wino):
+                sp = e["spec"]
+                wj[i] = (w.data_ptr(), scratch.data_ptr() + 4 * u_off[id(e)], begin, sp["O"], sp["C"], sp["transposed"], sp["mt"])
+                begin += sp["O"] * sp["C"]
+            seg = 0
+            for i, (w, e, _) in enumerate(plain):
+                sp = e["spec"]
+                Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
+                src = scratch.data_ptr() + 4 * u_off[id(e)] if sp["how"] == "wino" else w.data_ptr()
+                sj[i] = (src, e["buf"].data_ptr(), seg, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0,
+                         sp.get("RS", 1), sp["batch"])
+                seg += sp["batch"] * Np * (sp["K"] // 8)
+            tab.update(seg=seg, n_wino=len(wino), wino_total=begin, sj=torch.from_numpy(sj.view(np.uint8).copy()).to(dev),
+                       wj=torch.from_numpy(wj.view(np.uint8).copy()).to(dev))
+            if scratch is not None:
+                tab["scratch"] = scratch
+        if tab["n_h"]:
+            tab.update(_rebuild2h_table(np, [(w, e) for w, e, _ in todo[n_plain:]], dev))
     if tab["n_wino"]:
         call("u2pl_wino_weight_multi_f32", tab["wj"], tab["n_wino"], tab["wino_total"])
     if tab["n_plain"]:
         call("u2pl_weight_split3_multi_f32", tab["sj"], tab["n_plain"], tab["seg"])
     if tab["n_h"]:
-        call("u2pl_weight_split2h_multi_f32", tab["sj_h"], tab["n_h"], tab["seg_h"])
+        call("u2pl_weight_rebuild2h_f32", tab["rj"], tab["n_flat"], tab["n_rwino"], tab["seg_h"], tab["amax_h"], tab["mblk"], tab["pblk"])
     ev = torch.cuda.Event()
     ev.record(cur)
     for w, e, stamp in todo:
