@@ -215,6 +215,11 @@ int u2pl_predict_entropy_f32(const float* in, long sn, long sc, long sh, long sw
 int u2pl_reliable_map_u8(unsigned char* label, const float* entropy, const unsigned* thr_bits, long n,
                          const unsigned char* palette, unsigned char* rgb, unsigned char* heat, float heat_scale,
                          unsigned* ndropped, hipStream_t stream);
+/* out[i] = lut256[in[i]] for n bytes of device memory (lut256: uint8 [256], device): the label maps of
+ * u2pl_predict_map_f32 / u2pl_reliable_map_u8 in the dataset's raw ids (--raw_ids).  Any n, any alignment of in and out
+ * (16-byte loads and stores between an unaligned head and tail); out == in is allowed, a partial overlap is not.
+ * A NULL pointer: 1001. */
+int u2pl_lut_u8(const unsigned char* in, unsigned char* out, long n, const unsigned char* lut256, hipStream_t stream);
 
 /* ---- conv.hip (implicit GEMM on v_mfma_f32_32x32x2_f32) -------------------- */
 /* nn.Conv2d forward (NHWC rows, weights [Cout][R][S][Cin]): resnet.py:25-41,178-186;
@@ -615,6 +620,15 @@ int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned char* lab, c
                            const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
                            const float* mean3, const float* std3, const float* blur_w, float* scratch, float* out_img,
                            long long* out_lab, hipStream_t stream);
+/* u2pl_augment_ex_u8_f32 with dataset.label_map fused into the label read: every SOURCE label byte v becomes lut256[v]
+   (uint8 [256] on the device; the host validates that each entry is < num_classes or == ignore_label, so no other value
+   can reach a loss kernel whatever the files hold).  The map applies at load, before any transform: the crop's padding
+   still writes 0 and rotated-out pixels ignore_label, both in mapped space, neither looked up.  Image output: the bits of
+   u2pl_augment_ex_u8_f32; with the identity table the labels too.  lut256 == NULL: 1001. */
+int u2pl_augment_lut_u8_f32(const unsigned char* img, const unsigned char* lab, const long long* offsets,
+                            const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
+                            const unsigned char* lut256, const float* mean3, const float* std3, const float* blur_w,
+                            float* scratch, float* out_img, long long* out_lab, hipStream_t stream);
 
 /* ---- fp16 prediction path (csrc/half.hip): eval-mode forward with fp16 activations and weights.
    Activations are NHWC rows of IEEE fp16 (unsigned short bit patterns) with a pitch in elements; gfx950 only. ---- */

@@ -6,7 +6,9 @@ run through the network once, and its prediction written to <save_folder>/gray/<
 the forward pass on the fp16 path; --flip / --prob, test-time fusion of the image with its mirror image / of
 class probabilities instead of logits; --entropy, the softmax entropy of every pixel as an 8-bit heat map in
 <save_folder>/entropy/<stem>.png (255 = log C); --drop_percent P, gray/ and color/ hold the labels as the method's own
-pseudo-label rule would keep them: the P per cent lowest-entropy pixels of each image, the rest 255."""
+pseudo-label rule would keep them: the P per cent lowest-entropy pixels of each image, the rest 255.
+dataset.type pairs / pairs_semi: `image_path [label_path]` lines (labels are not read), input scale dataset.val.crop.size,
+colours dataset.colormap (default generic), --raw_ids: gray/ in the dataset's raw label ids."""
 import argparse
 import os
 import sys
@@ -28,10 +30,10 @@ def get_parser():
     return p
 
 
-def get_cli_parser(fusion=False, reliability=False):
+def get_cli_parser(fusion=False, reliability=False, raw_ids=False):
     """get_parser() keeps the reference's surface; the options only this project has are added here: --half, with
     fusion=True the test-time fusion options --flip and --prob, and with reliability=True as well (what main() parses)
-    --drop_percent and --entropy"""
+    --drop_percent and --entropy, and with raw_ids=True as well (main() too) --raw_ids"""
     p = get_parser()
     p.add_argument("--half", action="store_true", default=False,
                    help="forward pass with fp16 activations and weights (u2pl_amd.half); an image whose pass saturates is "
@@ -48,6 +50,10 @@ def get_cli_parser(fusion=False, reliability=False):
                             "(trainer.unsupervised.drop_percent's meaning; P in [0, 100])")
         p.add_argument("--entropy", action="store_true", default=False,
                        help="write the per-pixel softmax entropy as an 8-bit heat map to <save_folder>/entropy/<stem>.png")
+    if reliability and raw_ids:
+        p.add_argument("--raw_ids", action="store_true", default=False,
+                       help="write gray/ in the dataset's raw label ids (the inverse of dataset.label_map; dropped pixels get "
+                            "the raw ignore value) -- paired-list dataset types only")
     return p
 
 
@@ -55,26 +61,32 @@ def main():
     from PIL import Image
     from tqdm import tqdm
 
-    from eval import data_list
+    from eval import data_list, raw_id_table
     from u2pl_amd import infer as I
     from u2pl_amd.engine import load_state
     from u2pl_amd.models.model_helper import ModelBuilder
 
-    args = get_cli_parser(fusion=True, reliability=True).parse_args()
+    args = get_cli_parser(fusion=True, reliability=True, raw_ids=True).parse_args()
     cfg = yaml.load(open(args.config), Loader=yaml.Loader)
     ds = cfg["dataset"]
     gray, color = os.path.join(args.save_folder, "gray"), os.path.join(args.save_folder, "color")
     os.makedirs(gray, exist_ok=True)
     os.makedirs(color, exist_ok=True)
     items = data_list(cfg)
+    raw_lut = raw_id_table(cfg, args.raw_ids)
+    if raw_lut is not None:
+        raw_lut = torch.from_numpy(raw_lut).cuda()
     cfg["net"]["sync_bn"] = False
     model = ModelBuilder(cfg["net"])
     ck = torch.load(args.model_path, map_location="cpu")
     load_state(args.model_path, model, key="teacher_state" if "teacher_state" in ck else "model_state")
     model = model.cuda().eval()
-    input_scale = args.input_scale or ([769, 769] if "cityscapes" in ds["val"]["data_root"] else [513, 513])
+    if ds["type"].startswith("pairs"):
+        input_scale = args.input_scale or list(ds["val"]["crop"]["size"])
+    else:
+        input_scale = args.input_scale or ([769, 769] if "cityscapes" in ds["val"]["data_root"] else [513, 513])
     lut = torch.from_numpy(I.normalise_lut(ds["mean"], ds["std"])).cuda()
-    palette = torch.from_numpy(I.colormap("pascal")).cuda()
+    palette = torch.from_numpy(I.dataset_colormap(ds, "pascal")).cuda()
     half = None
     if args.half:
         from u2pl_amd.half import HalfPredictor
@@ -88,8 +100,12 @@ def main():
     dropped = []       # (ndropped device tensor, pixels) per image: read once, after the loop
     for image_path, _ in tqdm(items):
         name = image_path.split("/")[-1]
+        if ds["type"].startswith("pairs"):      # any image format: index maps go to a lossless file
+            name = os.path.splitext(name)[0] + ".png"
         img = torch.from_numpy(np.array(Image.open(image_path).convert("RGB"))).cuda()
         kw = dict(drop_percent=args.drop_percent, entropy=args.entropy) if reliability else {}
+        if raw_lut is not None:
+            kw["raw_lut"] = raw_lut
         out = I.infer_image(model, img, lut, input_scale, palette, half=half, flip=args.flip, prob=args.prob, **kw)
         label, rgb = out[:2]
         Image.fromarray(rgb.cpu().numpy()).save(os.path.join(color, name))

@@ -16,6 +16,13 @@
 //                           fp32, zeros where the window leaves the frame;  pass B (k_augment_blur) reads 25 taps of it
 //                           per output pixel (x fastest per lane in both passes, so scratch traffic is coalesced) and
 //                           writes the label.  A sample whose blur coin fell the other way reads the centre tap only.
+//
+// Label table (u2pl_augment_lut_u8_f32, dataset.label_map): the kernels that write labels carry a template switch LUT; with
+// it the ONE read of a source label byte (resize_lab) goes through a 256-entry uint8 table in device memory.  The index
+// is a byte, so the lookup cannot leave the table; padding (0) and rotated-out pixels (ignore_label) are written in
+// mapped space and are not looked up.  The table is read through the vector cache, not staged in LDS: it
+// is two 128-byte lines that every wave of the launch keeps hot, the lookup follows a gather of the same kind (the label
+// byte), and without the switch the kernels are the code they were -- no LDS, no barrier.
 #include "common.h"
 #include "u2pl_hip.h"
 
@@ -48,9 +55,12 @@ __device__ __forceinline__ AugSrc aug_src(const unsigned char* img, const unsign
 }
 
 // label of pixel (ry, rx) of the resized frame: legacy nearest, src = min(floor(dst * float(in/out)), in-1)
-__device__ __forceinline__ int resize_lab(const AugSrc& s, int ry, int rx) {
+// LUT: the byte indexes the 256-entry table of dataset.label_map -- the only place a source label is read
+template <bool LUT>
+__device__ __forceinline__ int resize_lab(const AugSrc& s, const unsigned char* __restrict__ lut, int ry, int rx) {
     const int ly = nearest_src(ry, (float)s.H / (float)s.rh, s.H), lx = nearest_src(rx, (float)s.W / (float)s.rw, s.W);
-    return s.lb[(long)ly * s.W + lx];
+    const unsigned char raw = s.lb[(long)ly * s.W + lx];
+    return LUT ? lut[raw] : raw;
 }
 
 // normalised pixel (ry, rx) of the resized frame, 0 <= ry < rh, 0 <= rx < rw: the arithmetic of k_augment (nn.hip)
@@ -117,20 +127,22 @@ __device__ __forceinline__ void rot_px(const AugSrc& s, const AugNorm& n, int ry
 }
 
 // label of pixel (ry, rx) of the rotated frame: grid_sample(nearest) = nearbyint, outside the frame -> ignore_label
-__device__ __forceinline__ int rot_lab(const AugSrc& s, int ry, int rx, int ignore_label) {
+template <bool LUT>
+__device__ __forceinline__ int rot_lab(const AugSrc& s, const unsigned char* __restrict__ lut, int ry, int rx,
+                                       int ignore_label) {
     double iy, ix;
     rot_coord(s, ry, rx, iy, ix);
     const double ny = rint(iy), nx = rint(ix);
     if (!(ny >= 0.0 && ny < (double)s.rh && nx >= 0.0 && nx < (double)s.rw)) return ignore_label;
-    return resize_lab(s, (int)ny, (int)nx);
+    return resize_lab<LUT>(s, lut, (int)ny, (int)nx);
 }
 
 // ---- no blur: one pass -------------------------------------------------------------------------------------------
-template <bool ROT>
+template <bool ROT, bool LUT>
 __global__ void k_augment_ex(const unsigned char* __restrict__ img, const unsigned char* __restrict__ lab,
                              const long long* __restrict__ off, const int* __restrict__ rec, int B, int H, int W, int Sh,
-                             int Sw, int ignore_label, AugNorm n, float* __restrict__ out_img,
-                             long long* __restrict__ out_lab) {
+                             int Sw, int ignore_label, const unsigned char* __restrict__ lut, AugNorm n,
+                             float* __restrict__ out_img, long long* __restrict__ out_lab) {
     const long total = (long)B * Sh * Sw;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % Sw);
@@ -145,10 +157,10 @@ __global__ void k_augment_ex(const unsigned char* __restrict__ img, const unsign
             if (s.flip) rx = s.rw - 1 - rx;
             if (ROT && (s.flags & U2PL_AUG_ROTATE)) {
                 rot_px(s, n, ry, rx, v);
-                l = rot_lab(s, ry, rx, ignore_label);
+                l = rot_lab<LUT>(s, lut, ry, rx, ignore_label);
             } else {
                 resize_px(s, n, ry, rx, v);
-                l = resize_lab(s, ry, rx);
+                l = resize_lab<LUT>(s, lut, ry, rx);
             }
         }
         const long plane = (long)Sh * Sw, o = (long)b * 3 * plane + (long)y * Sw + x;
@@ -188,9 +200,11 @@ __global__ void k_augment_stage(const unsigned char* __restrict__ img, const uns
 }
 
 // ---- blur, pass B: 25 taps of the scratch tile (F.conv2d, zero padding 2, over the rotated frame) + flip + crop + label --
+template <bool LUT>
 __global__ void k_augment_blur(const unsigned char* __restrict__ img, const unsigned char* __restrict__ lab,
                                const long long* __restrict__ off, const int* __restrict__ rec, int B, int H, int W,
-                               int Sh, int Sw, int ignore_label, const float* __restrict__ blur_w,
+                               int Sh, int Sw, int ignore_label, const unsigned char* __restrict__ lut,
+                               const float* __restrict__ blur_w,
                                const float* __restrict__ scratch, float* __restrict__ out_img,
                                long long* __restrict__ out_lab) {
     __shared__ float w[25];
@@ -209,7 +223,7 @@ __global__ void k_augment_blur(const unsigned char* __restrict__ img, const unsi
         long long l = 0;
         if (ry >= 0 && ry < s.rh && rx >= 0 && rx < s.rw) {
             if (s.flip) rx = s.rw - 1 - rx;
-            l = (s.flags & U2PL_AUG_ROTATE) ? rot_lab(s, ry, rx, ignore_label) : resize_lab(s, ry, rx);
+            l = (s.flags & U2PL_AUG_ROTATE) ? rot_lab<LUT>(s, lut, ry, rx, ignore_label) : resize_lab<LUT>(s, lut, ry, rx);
             // centre tap: tile row y + 2, tile column x + 2 (mirrored: Sw + 1 - x); every tap stays inside the tile
             const float* c0 = scratch + (long)b * 3 * Th * Tw + (long)(y + 2) * Tw + (s.flip ? Sw + 1 - x : x + 2);
 #pragma unroll
@@ -242,10 +256,12 @@ U2PL_API size_t u2pl_augment_ex_scratch_bytes(int B, int Sh, int Sw, int mode) {
     return (size_t)B * 3 * (size_t)(Sh + 4) * (size_t)(Sw + 4) * sizeof(float);
 }
 
-U2PL_API int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned char* lab, const long long* offsets,
-                                    const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
-                                    const float* mean3, const float* std3, const float* blur_w, float* scratch,
-                                    float* out_img, long long* out_lab, hipStream_t stream) {
+// both entry points: LUT selects the instantiations that map the source label through lut256
+template <bool LUT>
+static int augment_launch(const unsigned char* img, const unsigned char* lab, const long long* offsets, const int* records,
+                          int B, int H, int W, int Sh, int Sw, int ignore_label, int mode, const unsigned char* lut256,
+                          const float* mean3, const float* std3, const float* blur_w, float* scratch, float* out_img,
+                          long long* out_lab, hipStream_t stream) {
     const long total = (long)B * Sh * Sw;
     if (total <= 0) return 0;
     if (!img || !lab || !records || !mean3 || !std3 || !out_img || !out_lab) return U2PL_EINVAL;
@@ -257,15 +273,33 @@ U2PL_API int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned cha
         U2PL_LAUNCH(k_augment_stage, dim3(grid_for((long)B * (Sh + 4) * (Sw + 4), 256)), dim3(256), 0, stream, img, lab,
                     offsets, records, B, H, W, Sh, Sw, n, scratch);
         U2PL_LAUNCH_CHECK();
-        U2PL_LAUNCH(k_augment_blur, dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records, B, H, W,
-                    Sh, Sw, ignore_label, blur_w, (const float*)scratch, out_img, out_lab);
+        U2PL_LAUNCH(k_augment_blur<LUT>, dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records, B, H,
+                    W, Sh, Sw, ignore_label, lut256, blur_w, (const float*)scratch, out_img, out_lab);
     } else if (mode & U2PL_AUG_ROTATE) {
-        U2PL_LAUNCH(k_augment_ex<true>, dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records, B, H,
-                    W, Sh, Sw, ignore_label, n, out_img, out_lab);
+        U2PL_LAUNCH((k_augment_ex<true, LUT>), dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records,
+                    B, H, W, Sh, Sw, ignore_label, lut256, n, out_img, out_lab);
     } else {
-        U2PL_LAUNCH(k_augment_ex<false>, dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records, B, H,
-                    W, Sh, Sw, ignore_label, n, out_img, out_lab);
+        U2PL_LAUNCH((k_augment_ex<false, LUT>), dim3(grid_for(total, 256)), dim3(256), 0, stream, img, lab, offsets, records,
+                    B, H, W, Sh, Sw, ignore_label, lut256, n, out_img, out_lab);
     }
     U2PL_LAUNCH_CHECK();
     return 0;
+}
+
+U2PL_API int u2pl_augment_ex_u8_f32(const unsigned char* img, const unsigned char* lab, const long long* offsets,
+                                    const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
+                                    const float* mean3, const float* std3, const float* blur_w, float* scratch,
+                                    float* out_img, long long* out_lab, hipStream_t stream) {
+    return augment_launch<false>(img, lab, offsets, records, B, H, W, Sh, Sw, ignore_label, mode, nullptr, mean3, std3,
+                                 blur_w, scratch, out_img, out_lab, stream);
+}
+
+U2PL_API int u2pl_augment_lut_u8_f32(const unsigned char* img, const unsigned char* lab, const long long* offsets,
+                                     const int* records, int B, int H, int W, int Sh, int Sw, int ignore_label, int mode,
+                                     const unsigned char* lut256, const float* mean3, const float* std3,
+                                     const float* blur_w, float* scratch, float* out_img, long long* out_lab,
+                                     hipStream_t stream) {
+    if (!lut256) return U2PL_EINVAL;
+    return augment_launch<true>(img, lab, offsets, records, B, H, W, Sh, Sw, ignore_label, mode, lut256, mean3, std3,
+                                blur_w, scratch, out_img, out_lab, stream);
 }

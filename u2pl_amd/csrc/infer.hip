@@ -499,3 +499,55 @@ U2PL_API int u2pl_reliable_map_u8(unsigned char* label, const float* entropy, co
     U2PL_LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// out[i] = lut[in[i]] over n bytes (--raw_ids: class indices -> the dataset's raw ids; 255 -> the raw ignore value).  The
+// table sits in LDS: a thread looks up 16 bytes per 16-byte load, so lookups, not memory, set the pace, and the LDS
+// serves 64 byte gathers per instruction where the vector cache would take them a few lanes at a time.  The first
+// (-in) mod 16 bytes and the last n mod 16 are done bytewise by one thread; every chunk between is ONE aligned 16-byte load
+// and, when `out` is aligned like `in` (in place: always), one 16-byte store -- dwords or bytes otherwise.  A thread
+// has read its chunk before it writes it and no other thread touches it, so out == in is allowed (a partial overlap is not).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_lut_u8(const unsigned char* __restrict__ lut, const unsigned char* in, unsigned char* out, long n, long head, long body) {
+    __shared__ unsigned char s_lut[256];
+    s_lut[threadIdx.x] = lut[threadIdx.x];        // blockDim.x == 256
+    __syncthreads();
+    const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    for (long p = tid; p < body; p += (long)gridDim.x * blockDim.x) {
+        const long o = head + (p << 4);
+        const uint4 v = *(const uint4*)(in + o);
+        const unsigned src[4] = {v.x, v.y, v.z, v.w};
+        unsigned dst[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            dst[j] = (unsigned)s_lut[src[j] & 255u] | ((unsigned)s_lut[(src[j] >> 8) & 255u] << 8) |
+                     ((unsigned)s_lut[(src[j] >> 16) & 255u] << 16) | ((unsigned)s_lut[src[j] >> 24] << 24);
+        unsigned char* q = out + o;
+        if (((uintptr_t)q & 15) == 0) {
+            *(uint4*)q = make_uint4(dst[0], dst[1], dst[2], dst[3]);
+        } else if (((uintptr_t)q & 3) == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ((unsigned*)q)[j] = dst[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[j] = (unsigned char)(dst[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+    if (tid == 0) {
+        for (long i = 0; i < head; ++i) out[i] = s_lut[in[i]];
+        for (long i = head + (body << 4); i < n; ++i) out[i] = s_lut[in[i]];
+    }
+}
+
+U2PL_API int u2pl_lut_u8(const unsigned char* in, unsigned char* out, long n, const unsigned char* lut256,
+                         hipStream_t stream) {
+    if (!in || !out || !lut256) return U2PL_EINVAL;
+    if (n <= 0) return 0;
+    long head = (long)((16 - ((uintptr_t)in & 15)) & 15);
+    if (head > n) head = n;
+    const long body = (n - head) >> 4;
+    U2PL_LAUNCH(k_lut_u8, dim3(grid_for(body, 256, 1024)), dim3(256), 0, stream, lut256, in, out, n, head, body);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}

@@ -3,7 +3,9 @@ reference's per-sample CPU transform chain (augmentation.py:51-346, composed in 
 pascal_voc.py:48-71: ToTensor -> Normalize -> RandResize -> RandRotate -> RandomGaussianBlur ->
 RandomHorizontalFlip -> Crop) runs fused on the GPU: equal-sized batches of a config without rotation / blur as ONE
 gather (`u2pl_augment_u8_f32`), everything else -- the two options, batches of mixed image sizes (Pascal VOC) --
-through `u2pl_augment_ex_u8_f32`.  The random numbers are still drawn on the host with python `random` in the
+through `u2pl_augment_ex_u8_f32`.  A plan with a label table (`dataset.label_map`, the paired-list dataset types) takes
+`u2pl_augment_lut_u8_f32` for every batch: the same kernels with the table fused into the one read of a source label
+byte, so the device only ever sees table outputs.  The random numbers are still drawn on the host with python `random` in the
 reference's order, so a seeded run consumes the RNG stream exactly like `builder.Pipeline` does."""
 import random
 
@@ -20,7 +22,10 @@ ROTATE, BLUR = 1, 2         # U2PL_AUG_ROTATE / U2PL_AUG_BLUR
 class AugmentPlan:
     """Draws the per-sample geometry of builder.Pipeline.__call__ without touching pixels."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, lut=None):
+        # lut: np.uint8[256] of builder.build_label_lut (raw label byte -> class index), or None: labels are used as read
+        self.lut = None if lut is None else np.ascontiguousarray(lut, np.uint8).reshape(256).copy()
+        self._dev_lut = {}      # device -> the table
         self.mean = np.asarray(cfg["mean"], np.float32).copy()
         self.std = np.asarray(cfg["std"], np.float32).copy()
         self.rand_resize = cfg.get("rand_resize", False)
@@ -86,6 +91,14 @@ class AugmentPlan:
         self._dev[dev] = (wts, scratch)
         return wts, scratch
 
+    def _device_lut(self, dev):
+        """the label table on the device, copied once per device"""
+        t = self._dev_lut.get(dev)
+        if t is None:
+            from ..hipops import h2d
+            t = self._dev_lut[dev] = h2d(torch.from_numpy(self.lut), dev)
+        return t
+
 
 def widen(params, h, w):
     """(B,8) option-free records -> (B,16) wide records of samples that are all h x w (or per-sample sizes)"""
@@ -102,6 +115,8 @@ def augment_batch(plan, images_u8, labels_u8, params, offsets=None, device=None)
     Packed form (RawSegDataset.collate_fn, samples of different sizes): images_u8 / labels_u8 flat uint8 buffers,
     params (B,16) int32 with each sample's size, offsets (B,) int64 = first PIXEL of each sample.
     Tensors still on the host (pinned by the DataLoader) are copied to `device` without blocking.
+    With plan.lut every batch, option-free dense ones included, takes u2pl_augment_lut_u8_f32: labels_u8 are the RAW bytes of
+    the label files and the output labels their table images; without it the calls are the ones made before the table existed.
     -> (B,3,Sh,Sw) float32 normalised crops, (B,Sh,Sw) int64 labels."""
     from ..hipops import h2d
 
@@ -120,7 +135,7 @@ def augment_batch(plan, images_u8, labels_u8, params, offsets=None, device=None)
     else:
         B, H, W, _ = images_u8.shape
     Sh, Sw = plan.out_size()
-    old_entry = not packed and not plan.mode and params.shape[1] == 8
+    old_entry = not packed and not plan.mode and params.shape[1] == 8 and plan.lut is None
     if not old_entry and params.shape[1] == 8:
         params = widen(params.cpu(), H, W)
     images_u8, labels_u8 = (t if t.is_cuda else t.to(dev, non_blocking=True) for t in (images_u8, labels_u8))
@@ -135,6 +150,11 @@ def augment_batch(plan, images_u8, labels_u8, params, offsets=None, device=None)
              plan.mean.ctypes.data, plan.std.ctypes.data, out, lab)
         return out, lab
     wts, scratch = plan._device_buffers(dev, B) if plan.mode & BLUR else (None, None)
+    if plan.lut is not None:
+        call("u2pl_augment_lut_u8_f32", images_u8.contiguous(), labels_u8.contiguous(), offsets, params, B, H, W, Sh, Sw,
+             plan.ignore_label, plan.mode, plan._device_lut(dev), plan.mean.ctypes.data, plan.std.ctypes.data, wts, scratch,
+             out, lab)
+        return out, lab
     call("u2pl_augment_ex_u8_f32", images_u8.contiguous(), labels_u8.contiguous(), offsets, params, B, H, W, Sh, Sw,
          plan.ignore_label, plan.mode, plan.mean.ctypes.data, plan.std.ctypes.data, wts, scratch, out, lab)
     return out, lab
@@ -159,8 +179,11 @@ class RawSegDataset(torch.utils.data.Dataset):
         ip, lp = self.base.samples[i]
         with open(os.path.join(self.base.root, ip), "rb") as f:
             image = np.asarray(Image.open(f).convert("RGB")).copy()
-        with open(os.path.join(self.base.root, lp), "rb") as f:
-            label = np.asarray(Image.open(f).convert("L")).copy()
+        if self.base.kind == "pairs":   # raw bytes (checked against `other: error`): the table is applied on the GPU
+            label = self.base.raw_label(lp, image.shape[0], image.shape[1]).copy()
+        else:
+            with open(os.path.join(self.base.root, lp), "rb") as f:
+                label = np.asarray(Image.open(f).convert("L")).copy()
         params = self.plan.draw(image.shape[0], image.shape[1])
         return torch.from_numpy(image), torch.from_numpy(label), torch.from_numpy(params)
 

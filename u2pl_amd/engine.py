@@ -148,7 +148,7 @@ def absolutize_paths(cfg, exp_path):
             d[key] = osp.normpath(osp.join(exp_path, d[key]))
     ds = cfg["dataset"]
     for sub in (ds, ds.get("train", {}), ds.get("val", {})):
-        for key in ("data_root", "data_list"):
+        for key in ("data_root", "data_list", "unlabeled_list"):
             fix(sub, key)
     if isinstance(cfg.get("saver", {}).get("pretrain"), str):
         fix(cfg["saver"], "pretrain")

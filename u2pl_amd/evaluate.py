@@ -139,7 +139,7 @@ def _iou(hist3c):
 
 @torch.no_grad()
 def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=True, ignore=255, on_prediction=None,
-             palette=None, half=None, flip=False, prob=False, drop_percent=None, entropy=False):
+             palette=None, half=None, flip=False, prob=False, drop_percent=None, entropy=False, raw_lut=None):
     """samples: iterable of (image (3,h,w) float tensor already mean/std normalised, label (h,w) integer array).
     Returns (mIoU, per-class IoU).  on_prediction(i, uint8 map) receives every argmax map (gray dumps); with a
     palette ((256,3) uint8, array or tensor) it is called as on_prediction(i, gray, color): both maps come from one
@@ -152,7 +152,9 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
     without entropy=True).  With drop_percent the return value is (mIoU, IoU, rel): mIoU / IoU are those of the unfiltered
     arg-max as before, and rel = dict(miou_reliable, iou_reliable, miou_unreliable, iou_unreliable, coverage = kept pixels
     over non-ignored pixels, hist_reliable, hist_unreliable = the (3, classes) integer counts) from a second confusion
-    histogram on the target with the unreliable pixels set to `ignore`; unreliable = total - reliable."""
+    histogram on the target with the unreliable pixels set to `ignore`; unreliable = total - reliable.
+    raw_lut (--raw_ids): (256,) uint8 table class -> raw id (builder.raw_id_lut); the gray map handed to on_prediction goes
+    through it on the device (H.lut_u8, in place).  Colours and every IoU stay in class space."""
     H.check_drop_percent(drop_percent)
     model.eval()
     dev = next(model.parameters()).device
@@ -160,6 +162,8 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
     hist_rel = torch.zeros(3 * classes, dtype=torch.int64, device=dev) if drop_percent is not None else None
     if palette is not None:
         palette = torch.as_tensor(palette).to(dev)
+    if raw_lut is not None:
+        raw_lut = torch.as_tensor(raw_lut).to(dev)
     for i, (image, label) in enumerate(samples):
         image = torch.as_tensor(image, dtype=torch.float32).unsqueeze(0).to(dev)
         logits = predict_image(model, image, classes, base_size, crop, scales, use_crop, half, flip, prob)
@@ -175,13 +179,18 @@ def evaluate(model, samples, classes, base_size, crop, scales=(1.0,), use_crop=T
                 H.drop_high_entropy_(kept, rel["entropy"], rel["threshold"], ignore)
                 call("u2pl_confusion_hist_f32", logits.contiguous(), kept, ignore, 1, classes, h, w, hist_rel)
             if on_prediction is not None:
+                if raw_lut is not None:
+                    H.lut_u8(gray, raw_lut)
                 maps = [gray[0].cpu().numpy()] + ([] if color is None else [color[0].cpu().numpy()])
                 on_prediction(i, *maps, None if rel["heat"] is None else rel["heat"].cpu().numpy())
         elif on_prediction is not None and palette is not None:
             gray, color = H.predict_map(logits.unsqueeze(0), (h, w), palette)
+            if raw_lut is not None:
+                H.lut_u8(gray, raw_lut)
             on_prediction(i, gray[0].cpu().numpy(), color[0].cpu().numpy())
         elif on_prediction is not None:
-            on_prediction(i, logits.argmax(0).to(torch.uint8).cpu().numpy())
+            gray = logits.argmax(0).to(torch.uint8)
+            on_prediction(i, (gray if raw_lut is None else H.lut_u8(gray.contiguous(), raw_lut)).cpu().numpy())
     hh = hist.cpu().double().reshape(3, classes)
     inter, union = hh[0], hh[1] + hh[2] - hh[0]
     iou = (inter / (union + 1e-10)).numpy()

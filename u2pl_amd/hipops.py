@@ -112,6 +112,23 @@ def predict_map(logits_low, size, palette=None):
     return label, rgb
 
 
+def lut_u8(x, lut, out=None):
+    """out[i] = lut[x[i]] over a contiguous uint8 tensor (u2pl_lut_u8); lut: (256,) uint8 on the same device.  out=None
+    writes in place (out is x); -> out.  --raw_ids: class indices to the dataset's raw ids."""
+    _chk_cuda(x, lut, out)
+    if tuple(lut.shape) != (256,):
+        raise _lib.HipError("lut: expected shape (256,)")
+    lut = _u8c(lut, "lut")
+    if x.dtype != torch.uint8 or not x.is_contiguous():
+        raise _lib.HipError("lut_u8: expected a contiguous uint8 tensor")
+    if out is None:
+        out = x
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != x.numel():
+        raise _lib.HipError("lut_u8: out must be a contiguous uint8 tensor of x's size")
+    call("u2pl_lut_u8", x, out, x.numel(), lut)
+    return out
+
+
 def window_fuse(pred, count, logits, origin, size, flip=False, softmax=False, weight=1.0, bump=True):
     """One view of test-time flip / probability fusion, in place: F.interpolate(logits, size, 'bilinear',
     align_corners=True), mirrored back along the width when flip, softmax over the classes when softmax, times weight,

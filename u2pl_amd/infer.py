@@ -8,7 +8,9 @@
                                      fp16 path (u2pl_amd.half), redone in fp32 when it saturated; flip= / prob=: the
                                      views fused at the image size (eval.py:166-180, commented out upstream);
                                      drop_percent= / entropy=: entropy map and labels filtered by it (loss_helper.py:35-43)
-  colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables
+  colormap        utils.py:639-700   Pascal VOC / Cityscapes label colours as (256, 3) uint8 tables; "generic": the VOC
+                                     rule over all 256 rows, 256 distinct colours for any class count
+  dataset_colormap                   the table a config asks for (dataset.colormap) or gets by default
 """
 import numpy as np
 import torch
@@ -22,9 +24,14 @@ _CITYSCAPES = [(128, 64, 128), (244, 35, 232), (70, 70, 70), (102, 102, 156), (1
 
 
 def colormap(name):
-    """(256, 3) uint8 table of `name` ("pascal" | "cityscapes").  Pascal: the VOC devkit's rule for classes 0..20 (bit
+    """(256, 3) uint8 table of `name` ("pascal" | "cityscapes" | "generic").  Pascal: the VOC devkit's rule for classes 0..20 (bit
     3j + k of the class index becomes bit 7 - j of channel k), every other row 255; Cityscapes: the 19 train-id colours,
-    every other row 0 -- the rows the reference's tables leave at their fill value."""
+    every other row 0 -- the rows the reference's tables leave at their fill value.  Generic: the devkit's rule for all 256
+    rows; it spreads the 8 bits of the index over 3 channels one to one, so the rows are distinct, and rows 0..20 are Pascal's."""
+    if name == "generic":
+        i = np.arange(256)[:, None, None]
+        j, k = np.arange(3)[None, :, None], np.arange(3)[None, None, :]
+        return ((((i >> (3 * j + k)) & 1) << (7 - j)).sum(1)).astype(np.uint8)
     if name == "pascal":
         cm = np.full((256, 3), 255, np.uint8)
         for i in range(21):
@@ -37,6 +44,12 @@ def colormap(name):
     raise ValueError(f"unknown colour map {name!r}")
 
 
+def dataset_colormap(ds, default):
+    """dataset.colormap ("pascal" | "cityscapes" | "generic") -> table; without the key "generic" for the paired-list
+    types and `default` -- what the script has always used -- for the two reference types"""
+    return colormap(ds.get("colormap", "generic" if ds["type"].startswith("pairs") else default))
+
+
 def normalise_lut(mean, std):
     """(3, 256) float32: [c][v] = (v - mean[c]) / std[c].  As in the reference the byte value is a float32 and mean / std
     are Python lists, so numpy evaluates the expression in float64; the result is rounded to float32 once."""
@@ -46,7 +59,7 @@ def normalise_lut(mean, std):
 
 @torch.no_grad()
 def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=False, prob=False, drop_percent=None,
-                entropy=False):
+                entropy=False, raw_lut=None):
     """img_u8 (h,w,3) uint8, lut (3,256) float32, palette (256,3) uint8 or None: GPU tensors.
     -> (label (h,w) uint8, rgb (h,w,3) uint8 or None, pred = the decoder's low-resolution logits).
     half: a u2pl_amd.half.HalfPredictor of `model` -- the forward pass runs with fp16 activations and weights, and the
@@ -61,7 +74,9 @@ def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=F
     (h,w) or None, threshold, ndropped: one-element device tensors or None).  drop_percent = P in [0, 100] has the meaning
     of trainer.unsupervised.drop_percent, the share kept: the pixels whose entropy reaches np.percentile(entropy, P) become
     255 in label and take palette[255] in rgb.  entropy=True adds the heat map (255 = log C) and leaves label / rgb as they
-    are without it."""
+    are without it.
+    raw_lut (--raw_ids): (256,) uint8 device table class -> raw id (builder.raw_id_lut); label is rewritten through it in
+    place (H.lut_u8) after the colours were looked up, so rgb stays in class space."""
     H.check_drop_percent(drop_percent)
     h, w = img_u8.shape[:2]
     x = H.infer_input(img_u8, lut, input_scale)
@@ -89,6 +104,8 @@ def infer_image(model, img_u8, lut, input_scale, palette=None, half=None, flip=F
         label, rgb, rel = H.predict_reliable(pred, (h, w), prob, palette, drop_percent, entropy)
     else:
         label, rgb = H.predict_map(pred, (h, w), palette)     # straight to the image size, not through the input scale
+    if raw_lut is not None:
+        H.lut_u8(label, raw_lut)
     out = (label[0], None if rgb is None else rgb[0], pred)
     if half is not None:
         out += (fell_back,)

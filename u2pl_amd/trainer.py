@@ -97,6 +97,14 @@ def classmix(image, label, conf, sel):
     return oi, ol, oc
 
 
+def head_lr_times(d):
+    """learning-rate multiplier of decoder and aux head: 10 for Pascal VOC, 1 for Cityscapes (train_semi.py:100-110); the
+    paired-list types (`pairs`, `pairs_semi`) take `dataset.head_lr_times`, default 1 -- the two reference types ignore the key"""
+    if d["type"].startswith("pairs"):
+        return d.get("head_lr_times", 1)
+    return 10 if d["type"].startswith("pascal") else 1
+
+
 class SemiTrainer:
     def __init__(self, cfg, model, model_teacher, sup_loss_fn, steps_per_epoch, memobank=None):
         self.cfg = cfg
@@ -108,7 +116,7 @@ class SemiTrainer:
         self.epochs = tr["epochs"]
         self.sup_only_epoch = tr.get("sup_only_epoch", 1)
         self._init_schedule(tr)
-        times = 10 if cfg["dataset"]["type"].startswith("pascal") else 1  # train_semi.py:100-110
+        times = head_lr_times(cfg["dataset"])  # train_semi.py:100-110
         groups = [list(model.encoder.parameters()), list(model.decoder.parameters())]
         tgroups = [list(model_teacher.encoder.parameters()), list(model_teacher.decoder.parameters())]
         self.lr_mult = [1, times]
@@ -437,7 +445,7 @@ class SupTrainer:
         tr = cfg["trainer"]
         self.epochs = tr["epochs"]
         self._init_schedule(tr)
-        times = 10 if cfg["dataset"]["type"].startswith("pascal") else 1
+        times = head_lr_times(cfg["dataset"])
         groups = [list(model.encoder.parameters()), list(model.decoder.parameters())]
         self.lr_mult = [1, times]
         if hasattr(model, "auxor"):
