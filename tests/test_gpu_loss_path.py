@@ -114,6 +114,31 @@ def test_select_kth_ohem_rule():
 
 
 # ------------------------------------------------------------------ unsup loss (a11)
+# The sampled gradients of the goldens are held to the gradient's own scale, not to an absolute 1e-6 (about 1 % of an element).
+# What the golden's fp32 generation carries, measured on each fixture's own inputs: torch fp32 F.cross_entropy (which reproduces
+# the stored gradients bit for bit) against tests/loss_bounds.ce_ref in float64, largest element error in units of EPS scale,
+# scale = the per-pixel gradient scale (unsup: B H W / n_valid^2; OHEM: 1 / n_kept, the aux head 0.4 / n_kept):
+#   unsup_65_c19 3.89   unsup_97_c21 4.66   ohem_65_k3000 7.02 (aux 3.89)   ohem_65_kbig 4.82 (aux 3.99)   ohem_65_k60 3.83 (aux 2.77)
+# The tolerance is CAL_MARGIN (10) times that ceiling: 2e-10 to 1e-8 at these sizes.  Where the device's target differs from the
+# reference's in its one allowed pixel (Tier B), n differs by one: that pixel is left to the assertions above and 2 scale / n is
+# added for the others.
+UNSUP_GRAD_CEILING = {"65_c19": 3.89, "97_c21": 4.66}
+OHEM_GRAD_CEILING = {"65_k3000": (7.02, 3.89), "65_kbig": (4.82, 3.99), "65_k60": (3.83, 2.77)}
+
+
+def _sampled_grad_excess(grad, golden_sub, target_dev, target_ref, weight_num, ceiling, mult=1.0):
+    """largest |grad[:, :, ::5, ::5] - golden| over CAL_MARGIN ceiling EPS scale, scale = mult weight_num / n^2 (unsup weight:
+    weight_num = B H W) or mult / n (weight_num = 1), n = the reference's count of valid pixels"""
+    from contrast_bounds import CAL_MARGIN, EPS
+    n = int((np.asarray(target_ref) != 255).sum())
+    scale = mult * (weight_num / n if weight_num != 1.0 else 1.0) / n
+    flip = np.asarray(target_dev) != np.asarray(target_ref)
+    tol = CAL_MARGIN * ceiling * EPS * scale + (2 * scale / n if flip.any() else 0.0)
+    d = np.abs(grad[:, :, ::5, ::5].astype(np.float64) - golden_sub)
+    d = np.where(flip[:, None, ::5, ::5], 0.0, d)
+    return float(d.max() / tol)
+
+
 @pytest.mark.parametrize("tag", ["65_c19", "97_c21"])
 def test_unsup_loss_golden(tag):
     from u2pl_amd.utils.loss_helper import compute_unsupervised_loss
@@ -131,6 +156,7 @@ def test_unsup_loss_golden(tag):
     assert (target.cpu().numpy() != g["new_target"]).sum() <= 1          # Tier B (from logits)
     gr = predict.grad.cpu().numpy()
     assert np.abs(gr[:, :, ::5, ::5] - g["grad_sub"]).max() < 1e-6
+    assert _sampled_grad_excess(gr, g["grad_sub"], target.cpu().numpy(), g["new_target"], target.numel(), UNSUP_GRAD_CEILING[tag]) <= 1.0
     assert abs(np.abs(gr.astype(np.float64)).sum() - float(g["grad_abs_sum"])) < 1e-4 * max(1.0, float(g["grad_abs_sum"]))
     assert low_s.grad is not None and torch.isfinite(low_s.grad).all()
     # Tier A: reference entropy as fixed input -> bit-exact target overwrite
@@ -225,6 +251,11 @@ def test_ohem_golden(tag):
     gm = main.grad.cpu().numpy()
     assert np.abs(gm[:, :, ::5, ::5] - g["grad_main_sub"]).max() < 1e-6
     assert np.abs(aux.grad.cpu().numpy()[:, :, ::5, ::5] - g["grad_aux_sub"]).max() < 1e-6
+    for pred, sub, mult, ceil in ((main, g["grad_main_sub"], 1.0, OHEM_GRAD_CEILING[tag][0]), (aux, g["grad_aux_sub"], 0.4, OHEM_GRAD_CEILING[tag][1])):
+        kept = H.ohem_kept_target(pred.detach(), T(target), 0.7, int(g["min_kept"]), 255).cpu().numpy()
+        kept_ref = R.ohem_ce(pred.detach().cpu().numpy(), target, 0.7, int(g["min_kept"]))[1]
+        assert (kept != kept_ref).sum() <= 1
+        assert _sampled_grad_excess(pred.grad.cpu().numpy(), sub, kept, kept_ref, 1.0, ceil, mult) <= 1.0
     assert abs(int((np.abs(gm).sum(1) > 0).sum()) - int(g["n_kept_main"])) <= 1
 
 

@@ -223,7 +223,8 @@ __global__ void k_sel_pass(const float* __restrict__ v, long n, int nspec, const
 }
 
 // thresholds: numpy _lerp in float32 (no FMA): d=b-a; t>=.5 ? b-d*(1-t) : a+d*t.
-// kind 1 (OHEM): thr = kth > floor ? kth : floor, or +inf when min_kept > n_valid (loss_helper.py:513-515)
+// kind 1 (OHEM): thr = kth > floor ? kth : floor, or +inf (nothing dropped) when min_kept > n_valid (loss_helper.py:512-515) and
+// when min_kept <= 0 (loss_helper.py:519: the reference applies its threshold only inside `if self.min_kept > 0`)
 __global__ void k_sel_finish(int nspec, const int* __restrict__ kind, const float* __restrict__ q32,
                              const long long* __restrict__ kparam, const float* __restrict__ fparam,
                              unsigned* __restrict__ ws) {
@@ -241,7 +242,7 @@ __global__ void k_sel_finish(int nspec, const int* __restrict__ kind, const floa
         if (ws[0] == 0) thr = __uint_as_float(0x7fc00000u);
     } else {
         const long long nv = ws[0];
-        if (kparam[j] > nv) thr = __uint_as_float(0x7f800000u);
+        if (kparam[j] > nv || kparam[j] <= 0) thr = __uint_as_float(0x7f800000u);
         else thr = a > fparam[j] ? a : fparam[j];
     }
     ws[SEL_THR + j] = __float_as_uint(thr);
