@@ -430,6 +430,24 @@ int u2pl_bn_bwd_apply_amax_f32(const float* dy, long lddy, const float* x, long 
 int u2pl_bn_bwd_sums_mx_f32(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* invstd,
                             const float* gamma, const float* beta, const float* drop, long rows_per_image, long M, int C,
                             void* workspace, double* sums, hipStream_t stream);
+/* y = relu(BN(x) + res): the mask cannot be recomputed from x, so the forward leaves it as a bit plane and the backward reads
+ * the plane instead of y (1/32 of a stream).  unsigned bits[M][ldb], ldb >= C / 32: bit c % 32 of word [row][c / 32] = stored
+ * y[row][c] > 0 (after residual, ReLU and Dropout2d scale; NaN: 0); words beyond C / 32 of a row are not touched.  C % 32 == 0,
+ * else U2PL_EINVAL.  u2pl_bn_apply_bits_f32 = u2pl_bn_apply_amax_f32 (y_amax may be NULL) + the plane; the two backward entries
+ * are u2pl_bn_bwd_sums_f32 / u2pl_bn_bwd_apply_amax_f32 with (bits, ldb) in the place of (y, ldy): the same bytes out.
+ * u2pl_bn_apply_f32 / u2pl_bn_apply_amax_f32 with relu == 3 write the same plane packed behind y's last row, at
+ * (unsigned*)(y + M * ldy) with ldb = C / 32: the caller's y buffer holds M * C / 32 more words. */
+int u2pl_bn_apply_bits_f32(const float* x, long ldx, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                           const float* res, long ldr, int relu, const float* drop, long rows_per_image, float* y, long ldy, long M,
+                           int C, float* y_amax, unsigned* bits, long ldb, hipStream_t stream);
+int u2pl_bn_bwd_sums_bits_f32(const float* dy, long lddy, const float* x, long ldx, const unsigned* bits, long ldb,
+                              const float* mean, const float* invstd, const float* drop, long rows_per_image, long M, int C,
+                              void* workspace, double* sums, hipStream_t stream);
+int u2pl_bn_bwd_apply_bits_f32(const float* dy, long lddy, const float* x, long ldx, const unsigned* bits, long ldb,
+                               const float* mean, const float* invstd, const float* gamma, const float* drop, long rows_per_image,
+                               const double* sums, double count, float* dx, long lddx, float* dres, long lddr, long M, int C,
+                               const double* psums, float* gsink, float* bsink, int accumulate, float* dx_amax, float* dres_amax,
+                               hipStream_t stream);
 int u2pl_wino_input_amax_f32(const float* x, long ldx, int N, int H, int W, int C, int dil, int mt, float* V, float* v_amax,
                              hipStream_t stream);
 int u2pl_wino_output_bnact_amax_f32(const float* Mb, int N, int H, int W, int O, int dil, int mt, const float* bias, float* y,

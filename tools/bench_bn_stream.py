@@ -8,7 +8,9 @@ the same buffers, in the same process, the two alternating round by round.  Each
     python tools/bench_bn_stream.py --tag parent        # merges the run into profiles/bn_stream.json under that tag
     python tools/bench_bn_stream.py --tag new --step-ms 110.1 110.3 110.2      # also records bench.py's ms_per_step of that build
 
-Bytes are algorithmic: streams x M x C x 4 (per-channel vectors, partial sums and the maxima are left out: < 0.1 %)."""
+Bytes are algorithmic: streams x M x C x 4 (per-channel vectors, partial sums and the maxima are left out: < 0.1 %).  The
+`_bits` cases move the ReLU mask as a bit plane, 1/32 of a stream: it is left out of their bytes like the per-channel vectors, so
+their yardstick is the stream count WITHOUT the mask (the from-y cases beside them count y as a full stream)."""
 import argparse
 import ctypes
 import json
@@ -35,6 +37,7 @@ CASES = {
     "bn_apply": (1, 1), "bn_apply_relu": (1, 1), "bn_apply_res_relu": (2, 1),
     "bn_bwd_apply_mask_x": (2, 1), "bn_bwd_apply_mask_y_dres": (3, 2), "bn_bwd_apply_mask_x_pg": (2, 1),
     "bn_bwd_sums": (3, 0), "bn_bwd_sums_mx": (2, 0), "bn_stats": (1, 0), "colsum": (1, 0),
+    "bn_apply_res_relu_bits": (2, 1), "bn_bwd_sums_bits": (2, 0), "bn_bwd_apply_bits_dres": (2, 2), "bn_bwd_apply_bits": (2, 1),
 }
 
 
@@ -73,6 +76,7 @@ class BufferSet:
         self.ws = torch.empty(max(1, query("u2pl_colreduce_workspace_bytes", M, 1, C)), device=DEV, dtype=torch.uint8)
         self.out = torch.empty(2 * C, device=DEV, dtype=torch.float64)
         self.amax = torch.zeros(REPS, 2, 2048, device=DEV)
+        self.bits = torch.randint(-2 ** 31, 2 ** 31, (M * (C // 32),), device=DEV, generator=g, dtype=torch.int32)
 
 
 def launcher(case, M, C, sets):
@@ -82,7 +86,16 @@ def launcher(case, M, C, sets):
         b = sets[i % len(sets)]
         a0, a1, a2, a3, a4 = b.t
         ax, ar = b.amax[i % REPS, 0], b.amax[i % REPS, 1]
-        if case.startswith("bn_apply"):
+        if case == "bn_apply_res_relu_bits":
+            call("u2pl_bn_apply_bits_f32", a0, C, b.mean, b.invstd, b.gamma, b.beta, a1, C, 1, None, rpi, a2, C, M, C, ax, b.bits,
+                 C // 32)
+        elif case == "bn_bwd_sums_bits":
+            call("u2pl_bn_bwd_sums_bits_f32", a0, C, a1, C, b.bits, C // 32, b.mean, b.invstd, None, rpi, M, C, b.ws, b.out)
+        elif case.startswith("bn_bwd_apply_bits"):
+            dres = a3 if case.endswith("dres") else None
+            call("u2pl_bn_bwd_apply_bits_f32", a0, C, a1, C, b.bits, C // 32, b.mean, b.invstd, b.gamma, None, rpi, b.sums, float(M),
+                 a2, C, dres, C, M, C, None, None, None, 0, ax, ar if dres is not None else None)
+        elif case.startswith("bn_apply"):
             res = a1 if "res" in case else None
             y = a2 if res is not None else a1
             call("u2pl_bn_apply_amax_f32", a0, C, b.mean, b.invstd, b.gamma, b.beta, res, C, int(case != "bn_apply"), None, rpi, y,

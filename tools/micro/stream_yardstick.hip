@@ -70,6 +70,7 @@ extern "C" __attribute__((visibility("default"))) int stream_yardstick(int nr, i
         case 11: return launch<1, 1>(s, n4, st);
         case 20: return launch<2, 0>(s, n4, st);
         case 21: return launch<2, 1>(s, n4, st);
+        case 22: return launch<2, 2>(s, n4, st);
         case 30: return launch<3, 0>(s, n4, st);
         case 31: return launch<3, 1>(s, n4, st);
         case 32: return launch<3, 2>(s, n4, st);

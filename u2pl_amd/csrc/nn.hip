@@ -89,6 +89,13 @@ __device__ __forceinline__ float4 relu_mask_from_y(float4 g, float4 yy) {
     g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
     return g;
 }
+// the ReLU mask from a bit plane: unsigned bits[M][ldb], bit c % 32 of word [row][c / 32] = stored y[row][c] > 0 (written by
+// k_bn_apply_bits).  nib: the four bits of a thread's float4 column
+__device__ __forceinline__ float4 relu_mask_from_bits(float4 g, unsigned nib) {
+    g.x = (nib & 1u) ? g.x : 0.f; g.y = (nib & 2u) ? g.y : 0.f;
+    g.z = (nib & 4u) ? g.z : 0.f; g.w = (nib & 8u) ? g.w : 0.f;
+    return g;
+}
 // a wave-uniform global address stated as such (all active lanes hold the same value): the load takes its base from scalar registers
 __device__ __forceinline__ const U2PL_GLOBAL char* uniform_global(const void* p) {
     const unsigned long long v = (unsigned long long)p;
@@ -97,7 +104,8 @@ __device__ __forceinline__ const U2PL_GLOBAL char* uniform_global(const void* p)
     return (const U2PL_GLOBAL char*)(((unsigned long long)hi << 32) | lo);
 }
 // g = dy*[y>0]*drop ; v0 = g, v1 = g * xhat     (BN backward sums)
-// MASK 0: no ReLU, 1: the mask from y, 2: the mask from x (gamma, relu_beta: the forward's parameters); DROP: Dropout2d scales.
+// MASK 0: no ReLU, 1: the mask from y, 2: the mask from x (gamma, relu_beta: the forward's parameters), 3: the mask from the bit
+// plane the forward left (relu_mask_from_bits; the op's y / ldy then hold the plane and its pitch in words); DROP: Dropout2d scales.
 // Compile-time forms: the row loop is straight-line code with the per-channel operands in registers.
 // Three loads per row and 32 registers of sums: to stay at 6 waves per SIMD a row's address is the wave-uniform base of its
 // row group plus one 32-bit byte offset per tensor that the thread keeps (its row in the group, its column)
@@ -117,6 +125,8 @@ struct BnBwdOp {
             const float4 xv = ldg4(uniform_global(x + rowg * ldx) + ox);
             if (MASK == 1) g = relu_mask_from_y(g, ldg4(uniform_global(y + rowg * ldy) + oy));
             if (MASK == 2) g = relu_mask_from_x(g, xv, mu, is, ga, be);
+            if (MASK == 3)      // (the row's word through the same uniform base + 32-bit offset; 8 lanes share a word)
+                g = relu_mask_from_bits(g, *(const U2PL_GLOBAL unsigned*)(uniform_global((const unsigned*)y + rowg * ldy) + oy) >> (c & 31));
             if (DROP) { g = f4mul(g, ldg4(drop + (long)im.img * C + c)); im.next(); }
             v0 = g; v1 = f4mul(g, f4mul(f4sub(xv, mu), is));
         }
@@ -125,7 +135,8 @@ struct BnBwdOp {
         const int c = c4 * 4;
         Col k;
         k.dy = dy; k.lddy = lddy; k.x = x; k.ldx = ldx; k.y = y; k.ldy = ldy; k.drop = drop; k.c = c; k.C = C;
-        k.og = (unsigned)((rg * lddy + c) * 4); k.ox = (unsigned)((rg * ldx + c) * 4); k.oy = (unsigned)((rg * ldy + c) * 4);
+        k.og = (unsigned)((rg * lddy + c) * 4); k.ox = (unsigned)((rg * ldx + c) * 4);
+        k.oy = MASK == 3 ? (unsigned)((rg * ldy + (c >> 5)) * 4) : (unsigned)((rg * ldy + c) * 4);
         k.mu = ldg4(mean + c); k.is = ldg4(invstd + c);
         k.ga = MASK == 2 ? ldg4(gamma + c) : f4zero();
         k.be = MASK == 2 ? ldg4(relu_beta + c) : f4zero();
@@ -299,6 +310,13 @@ U2PL_API int u2pl_bn_bwd_sums_f32(const float* dy, long lddy, const float* x, lo
     if (y) return run_bn_bwd_sums<1>(dy, lddy, x, ldx, y, ldy, mean, invstd, nullptr, nullptr, drop, rows_per_image, M, C, workspace, sums, stream);
     return run_bn_bwd_sums<0>(dy, lddy, x, ldx, nullptr, 0, mean, invstd, nullptr, nullptr, drop, rows_per_image, M, C, workspace, sums, stream);
 }
+// the same with the mask from the forward's bit plane (u2pl_bn_apply_bits_f32) instead of y: reads dy, x and 1/32 of a stream
+U2PL_API int u2pl_bn_bwd_sums_bits_f32(const float* dy, long lddy, const float* x, long ldx, const unsigned* bits, long ldb,
+                                       const float* mean, const float* invstd, const float* drop, long rows_per_image,
+                                       long M, int C, void* workspace, double* sums, hipStream_t stream) {
+    if (C % 32 || !bits || ldb < C / 32) return U2PL_EINVAL;
+    return run_bn_bwd_sums<3>(dy, lddy, x, ldx, (const float*)bits, ldb, mean, invstd, nullptr, nullptr, drop, rows_per_image, M, C, workspace, sums, stream);
+}
 // the same for y = relu(BN(x)) WITHOUT reading y: the mask is recomputed from x (gamma, beta: the forward's parameters)
 U2PL_API int u2pl_bn_bwd_sums_mx_f32(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* invstd,
                                      const float* gamma, const float* beta, const float* drop, long rows_per_image, long M, int C,
@@ -462,11 +480,22 @@ static dim3 bn_grid(long M, int C, int blocks_per_cu) {       // blocks_per_cu: 
     return dim3(grid_for(M, BN_ROWS * tr, cap > 0 ? cap : 1), nslab);
 }
 
+// the word of a row's 32 channels from the 8 adjacent lanes that hold them (C % 32 == 0: a row's lanes start at a multiple of
+// 8, and the 8 lanes of a word are active together): nibble j of the word is lane j's, OR-ed over quads and half rows by DPP
+__device__ __forceinline__ unsigned mask_word8(float4 t) {
+    const unsigned nib = (t.x > 0.f ? 1u : 0u) | (t.y > 0.f ? 2u : 0u) | (t.z > 0.f ? 4u : 0u) | (t.w > 0.f ? 8u : 0u);
+    int w = (int)(nib << ((threadIdx.x & 7) * 4));
+    w |= __builtin_amdgcn_update_dpp(0, w, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+    w |= __builtin_amdgcn_update_dpp(0, w, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
+    w |= __builtin_amdgcn_update_dpp(0, w, 0x141, 0xF, 0xF, true);     // row_half_mirror: the other quad of the 8 lanes
+    return (unsigned)w;
+}
 // y = [relu]( (x - mean)*invstd*gamma + beta [+ res] ) [* drop[n][c]]
-template <int NR>   // NR rows of one column: xp, rp, yp point at the first, sx, sr, sy floats lie between two of them
+// BITS: also bit c % 32 of bp[c / 32] = stored y > 0 (NaN: 0), the backward's ReLU mask; sb words between two rows
+template <int NR, bool BITS>   // NR rows of one column: xp, rp, yp point at the first, sx, sr, sy floats lie between two of them
 __device__ __forceinline__ unsigned bn_apply_rows(const float* xp, long sx, const float* rp, long sr, float* yp, long sy,
                                                   const float* dropc, int C, ImageOf<long>& im, int relu, float4 mu, float4 is, float4 ga,
-                                                  float4 be, unsigned am) {
+                                                  float4 be, unsigned am, unsigned* bp, long sb) {
     float4 v[NR], a[NR];
 #pragma unroll
     for (int u = 0; u < NR; ++u) v[u] = *(const float4*)(xp + u * sx);
@@ -484,46 +513,79 @@ __device__ __forceinline__ unsigned bn_apply_rows(const float* xp, long sx, cons
         if (dropc) { t = f4mul(t, *(const float4*)(dropc + (long)im.img * C)); im.next(); }     // (a cached line)
         *(float4*)(yp + u * sy) = t;
         am = amax_bits4(am, t);
+        if (BITS) {
+            const unsigned w = mask_word8(t);
+            if ((threadIdx.x & 7) == 0) bp[u * sb] = w;
+        }
     }
     return am;
 }
+// the body of k_bn_apply / k_bn_apply_bits (one text, two kernels: the form without bits keeps its instructions)
+#define U2PL_BN_APPLY_BODY(BITS) \
+    const ColOwner o = col_owner(C);                                                                                                       \
+    unsigned am = 0u;                                                                                                                      \
+    if (o.active) {                                                                                                                        \
+        const int c = o.c;                                                                                                                 \
+        const float4 mu = *(const float4*)(mean + c), is = *(const float4*)(invstd + c);                                                   \
+        const float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);                                                    \
+        ImageOf<long> im;                                                                                                                  \
+        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);                                                 \
+        const float* dropc = drop ? drop + c : nullptr;                                                                                    \
+        const long sx = o.step * ldx, sr = o.step * ldr, sy = o.step * ldy;      /* (row bases stay 64-bit: tensors beyond 2^31 bytes) */  \
+        const float* xp = x + o.r * ldx + c;                                                                                               \
+        const float* rp = res ? res + o.r * ldr + c : nullptr;                                                                             \
+        float* yp = y + o.r * ldy + c;                                                                                                     \
+        const long sb = BITS ? o.step * ldb : 0;                                                                                           \
+        unsigned* bp = BITS ? bits + o.r * ldb + (c >> 5) : nullptr;                                                                       \
+        for (long r = o.r; r < M; r += o.chunk) {                                                                                          \
+            if (r + (BN_ROWS - 1) * o.step < M) {                                                                                          \
+                am = bn_apply_rows<BN_ROWS, BITS>(xp, sx, rp, sr, yp, sy, dropc, C, im, relu, mu, is, ga, be, am, bp, sb);                 \
+            } else {      /* the last chunk of the tensor */                                                                               \
+                for (int u = 0; r + u * o.step < M; ++u)                                                                                   \
+                    am = bn_apply_rows<1, BITS>(xp + u * sx, sx, rp ? rp + u * sr : nullptr, sr, yp + u * sy, sy, dropc, C, im, relu,      \
+                                                mu, is, ga, be, am, BITS ? bp + u * sb : nullptr, sb);                                     \
+            }                                                                                                                              \
+            im.jump();                                                                                                                     \
+            xp += o.chunk * ldx; yp += o.chunk * ldy;                                                                                      \
+            if (rp) rp += o.chunk * ldr;                                                                                                   \
+            if (BITS) bp += o.chunk * ldb;                                                                                                 \
+        }                                                                                                                                  \
+    }                                                                                                                                      \
+    if (y_amax) amax_wave_publish(am, y_amax);       /* (uniform branch, every lane; split-fp16: the output is a GEMM operand) */
 __global__ U2PL_BN_KERNEL(6) void k_bn_apply(const float* __restrict__ x, long ldx, const float* __restrict__ mean,
                            const float* __restrict__ invstd, const float* __restrict__ gamma,
                            const float* __restrict__ beta, const float* __restrict__ res, long ldr, int relu,
                            const float* __restrict__ drop, long rows_per_image, float* __restrict__ y, long ldy,
                            long M, int C, unsigned* __restrict__ y_amax) {
-    const ColOwner o = col_owner(C);
-    unsigned am = 0u;
-    if (o.active) {
-        const int c = o.c;
-        const float4 mu = *(const float4*)(mean + c), is = *(const float4*)(invstd + c);
-        const float4 ga = *(const float4*)(gamma + c), be = *(const float4*)(beta + c);
-        ImageOf<long> im;
-        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);
-        const float* dropc = drop ? drop + c : nullptr;
-        const long sx = o.step * ldx, sr = o.step * ldr, sy = o.step * ldy;      // (row bases stay 64-bit: tensors beyond 2^31 bytes)
-        const float* xp = x + o.r * ldx + c;
-        const float* rp = res ? res + o.r * ldr + c : nullptr;
-        float* yp = y + o.r * ldy + c;
-        for (long r = o.r; r < M; r += o.chunk) {
-            if (r + (BN_ROWS - 1) * o.step < M) {
-                am = bn_apply_rows<BN_ROWS>(xp, sx, rp, sr, yp, sy, dropc, C, im, relu, mu, is, ga, be, am);
-            } else {      // the last chunk of the tensor
-                for (int u = 0; r + u * o.step < M; ++u)
-                    am = bn_apply_rows<1>(xp + u * sx, sx, rp ? rp + u * sr : nullptr, sr, yp + u * sy, sy, dropc, C, im, relu, mu, is,
-                                          ga, be, am);
-            }
-            im.jump();
-            xp += o.chunk * ldx; yp += o.chunk * ldy;
-            if (rp) rp += o.chunk * ldr;
-        }
-    }
-    if (y_amax) amax_wave_publish(am, y_amax);       // (uniform branch, every lane; split-fp16: the output is a GEMM operand)
+    unsigned* const bits = nullptr; const long ldb = 0;
+    U2PL_BN_APPLY_BODY(false)
 }
+// the form that also leaves the ReLU mask of the stored y as a bit plane (C % 32 == 0)
+__global__ U2PL_BN_KERNEL(6) void k_bn_apply_bits(const float* __restrict__ x, long ldx, const float* __restrict__ mean,
+                           const float* __restrict__ invstd, const float* __restrict__ gamma,
+                           const float* __restrict__ beta, const float* __restrict__ res, long ldr, int relu,
+                           const float* __restrict__ drop, long rows_per_image, float* __restrict__ y, long ldy,
+                           long M, int C, unsigned* __restrict__ y_amax, unsigned* __restrict__ bits, long ldb) {
+    U2PL_BN_APPLY_BODY(true)
+}
+static int run_bn_apply_bits(const float* x, long ldx, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                             const float* res, long ldr, int relu, const float* drop, long rows_per_image, float* y, long ldy, long M,
+                             int C, float* y_amax, unsigned* bits, long ldb, hipStream_t stream) {
+    if (C % 32 || !bits || ldb < C / 32) return U2PL_EINVAL;
+    U2PL_LAUNCH(k_bn_apply_bits, bn_grid(M, C, 6), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
+                       beta, res, ldr, relu, drop, rows_per_image, y, ldy, M, C, (unsigned*)y_amax, bits, ldb);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+// relu: 0 off, 1 ReLU, 3 ReLU and the mask bits of the stored y packed behind y's last row: the plane of
+// u2pl_bn_apply_bits_f32 at (unsigned*)(y + M * ldy) with ldb = C / 32 (the caller's buffer holds M * C / 32 more words)
 U2PL_API int u2pl_bn_apply_f32(const float* x, long ldx, const float* mean, const float* invstd, const float* gamma,
                                const float* beta, const float* res, long ldr, int relu, const float* drop,
                                long rows_per_image, float* y, long ldy, long M, int C, hipStream_t stream) {
     if (C % 4) return U2PL_EINVAL;
+    if (relu & 2)
+        return run_bn_apply_bits(x, ldx, mean, invstd, gamma, beta, res, ldr, 1, drop, rows_per_image, y, ldy, M, C, nullptr,
+                                 (unsigned*)(y + M * ldy), C / 32, stream);
     U2PL_LAUNCH(k_bn_apply, bn_grid(M, C, 6), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
                        beta, res, ldr, relu, drop, rows_per_image, y, ldy, M, C, (unsigned*)nullptr);
     U2PL_LAUNCH_CHECK();
@@ -534,23 +596,42 @@ U2PL_API int u2pl_bn_apply_amax_f32(const float* x, long ldx, const float* mean,
                                     const float* beta, const float* res, long ldr, int relu, const float* drop,
                                     long rows_per_image, float* y, long ldy, long M, int C, float* y_amax, hipStream_t stream) {
     if (C % 4) return U2PL_EINVAL;
+    if (relu & 2)
+        return run_bn_apply_bits(x, ldx, mean, invstd, gamma, beta, res, ldr, 1, drop, rows_per_image, y, ldy, M, C, y_amax,
+                                 (unsigned*)(y + M * ldy), C / 32, stream);
     U2PL_LAUNCH(k_bn_apply, bn_grid(M, C, 6), dim3(256), 0, stream, x, ldx, mean, invstd, gamma,
                        beta, res, ldr, relu, drop, rows_per_image, y, ldy, M, C, (unsigned*)y_amax);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
+// the same + the ReLU mask of the stored y into unsigned bits[M][ldb] (ldb >= C / 32): bit c % 32 of word [row][c / 32] =
+// y[row][c] > 0, y as stored (after residual, ReLU and Dropout2d scale; NaN: 0).  C % 32 == 0; y_amax may be NULL.  Words
+// beyond C / 32 of a row are not written.  The backward reads the plane instead of y (u2pl_bn_bwd_*_bits_f32)
+U2PL_API int u2pl_bn_apply_bits_f32(const float* x, long ldx, const float* mean, const float* invstd, const float* gamma,
+                                    const float* beta, const float* res, long ldr, int relu, const float* drop,
+                                    long rows_per_image, float* y, long ldy, long M, int C, float* y_amax, unsigned* bits, long ldb,
+                                    hipStream_t stream) {
+    return run_bn_apply_bits(x, ldx, mean, invstd, gamma, beta, res, ldr, relu & 1, drop, rows_per_image, y, ldy, M, C, y_amax, bits,
+                             ldb, stream);
+}
 
 // g = dy*[y>0]*drop ; dres = g ; dx = gamma*invstd*(g - S0/cnt - xhat*S1/cnt)  (train)
 //                                dx = gamma*invstd*g                           (eval: sums == NULL)
 struct BnBwdCol { float4 mu, is, ga, be, gi, m0, m1; };      // a column's terms: gi = gamma*invstd, m0 = S0/cnt, m1 = S1/cnt
-template <int NR>   // NR rows of one column (pointers at the first row, s* floats between two rows); mode bits: 1 train, 2 mask from x
+// NR rows of one column (pointers at the first row, s* floats between two rows); mode bits: 1 train, 2 mask from x
+// BITS: the mask from the forward's bit plane (bp: the column's word of the first row, sb words between two rows, sh = c % 32)
+template <int NR, bool BITS>
 __device__ __forceinline__ void bn_bwd_rows(const float* gp, long sg, const float* xp, long sx, const float* yp, long sy, float* dxp,
                                             long sdx, float* drp, long sdr, const float* dropc, int C, ImageOf<long>& im, int mode,
-                                            const BnBwdCol& k, unsigned& am_x, unsigned& am_r) {
+                                            const BnBwdCol& k, unsigned& am_x, unsigned& am_r, const unsigned* bp, long sb, int sh) {
     float4 g[NR], xv[NR], yy[NR];
+    unsigned wd[NR];
 #pragma unroll
     for (int u = 0; u < NR; ++u) g[u] = *(const float4*)(gp + u * sg);
-    if (yp) {
+    if (BITS) {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) wd[u] = bp[u * sb];
+    } else if (yp) {
 #pragma unroll
         for (int u = 0; u < NR; ++u) yy[u] = *(const float4*)(yp + u * sy);
     }
@@ -561,7 +642,8 @@ __device__ __forceinline__ void bn_bwd_rows(const float* gp, long sg, const floa
 #pragma unroll
     for (int u = 0; u < NR; ++u) {
         float4 t = g[u];
-        if (yp) t = relu_mask_from_y(t, yy[u]);
+        if (BITS) t = relu_mask_from_bits(t, wd[u] >> sh);
+        else if (yp) t = relu_mask_from_y(t, yy[u]);
         else if (mode & 2) t = relu_mask_from_x(t, xv[u], k.mu, k.is, k.ga, k.be);   // (y = relu(BN(x)) without a residual)
         if (dropc) { t = f4mul(t, *(const float4*)(dropc + (long)im.img * C)); im.next(); }     // (a cached line)
         if (drp) *(float4*)(drp + u * sdr) = t;
@@ -579,6 +661,61 @@ __device__ __forceinline__ void bn_bwd_rows(const float* gp, long sg, const floa
         am_x = amax_bits4(am_x, o);
     }
 }
+// the body of k_bn_bwd_apply / k_bn_bwd_apply_bits (as U2PL_BN_APPLY_BODY)
+#define U2PL_BN_BWD_APPLY_BODY(BITS) \
+    unsigned am_x = 0u, am_r = 0u;                                                                                                                              \
+    if (psums && blockIdx.y == 0) {   /* (u2pl_bn_bwd_apply_pg_f32) the parameter gradients ride along: k_sums_to_f32's arithmetic, dgamma = S1, dbeta = S0 */  \
+        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < C; i += (long)gridDim.x * blockDim.x) {                                                  \
+            gsink[i] = (accumulate ? gsink[i] : 0.f) + (float)(psums[C + i] * (double)1.0f);                                                                    \
+            bsink[i] = (accumulate ? bsink[i] : 0.f) + (float)(psums[i] * (double)1.0f);                                                                        \
+        }                                                                                                                                                       \
+    }                                                                                                                                                           \
+    const ColOwner o = col_owner(C);                                                                                                                            \
+    if (o.active) {                                                                                                                                             \
+        const int c = o.c;                                                                                                                                      \
+        const int mode = (sums ? 1 : 0) | (!y && relu_beta ? 2 : 0);                                                                                            \
+        BnBwdCol k;                                                                                                                                             \
+        k.is = *(const float4*)(invstd + c); k.ga = *(const float4*)(gamma + c);                                                                                \
+        k.gi = f4mul(k.ga, k.is);                                                                                                                               \
+        k.mu = mode ? *(const float4*)(mean + c) : f4zero();                                                                                                    \
+        k.be = (mode & 2) ? *(const float4*)(relu_beta + c) : f4zero();                                                                                         \
+        k.m0 = f4zero(); k.m1 = f4zero();                                                                                                                       \
+        if (sums) {                                                                                                                                             \
+            k.m0 = make_float4((float)(sums[c] / count), (float)(sums[c + 1] / count), (float)(sums[c + 2] / count),                                            \
+                               (float)(sums[c + 3] / count));                                                                                                   \
+            k.m1 = make_float4((float)(sums[C + c] / count), (float)(sums[C + c + 1] / count), (float)(sums[C + c + 2] / count),                                \
+                               (float)(sums[C + c + 3] / count));                                                                                               \
+        }                                                                                                                                                       \
+        ImageOf<long> im;                                                                                                                                       \
+        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);                                                                      \
+        const float* dropc = drop ? drop + c : nullptr;                                                                                                         \
+        const long sg = o.step * lddy, sx = o.step * ldx, sy = o.step * ldy, sdx = o.step * lddx, sdr = o.step * lddr;                                          \
+        const float* gp = dy + o.r * lddy + c;                                                                                                                  \
+        const float* xp = x + o.r * ldx + c;                                                                                                                    \
+        const float* yp = y ? y + o.r * ldy + c : nullptr;                                                                                                      \
+        float* dxp = dx + o.r * lddx + c;                                                                                                                       \
+        float* drp = dres ? dres + o.r * lddr + c : nullptr;                                                                                                    \
+        const long sb = BITS ? o.step * ldb : 0;                                                                                                                \
+        const unsigned* bp = BITS ? bits + o.r * ldb + (c >> 5) : nullptr;                                                                                      \
+        const int sh = c & 31;                                                                                                                                  \
+        for (long r = o.r; r < M; r += o.chunk) {                                                                                                               \
+            if (r + (BN_ROWS - 1) * o.step < M) {                                                                                                               \
+                bn_bwd_rows<BN_ROWS, BITS>(gp, sg, xp, sx, yp, sy, dxp, sdx, drp, sdr, dropc, C, im, mode, k, am_x, am_r, bp, sb, sh);                          \
+            } else {      /* the last chunk of the tensor */                                                                                                    \
+                for (int u = 0; r + u * o.step < M; ++u)                                                                                                        \
+                    bn_bwd_rows<1, BITS>(gp + u * sg, sg, xp + u * sx, sx, yp ? yp + u * sy : nullptr, sy, dxp + u * sdx, sdx,                                  \
+                                         drp ? drp + u * sdr : nullptr, sdr, dropc, C, im, mode, k, am_x, am_r,                                                 \
+                                         BITS ? bp + u * sb : nullptr, sb, sh);                                                                                 \
+            }                                                                                                                                                   \
+            im.jump();                                                                                                                                          \
+            gp += o.chunk * lddy; xp += o.chunk * ldx; dxp += o.chunk * lddx;                                                                                   \
+            if (yp) yp += o.chunk * ldy;                                                                                                                        \
+            if (drp) drp += o.chunk * lddr;                                                                                                                     \
+            if (BITS) bp += o.chunk * ldb;                                                                                                                      \
+        }                                                                                                                                                       \
+    }                                                                                                                                                           \
+    if (dx_amax) amax_wave_publish(am_x, dx_amax);                                                                                                              \
+    if (dres_amax) amax_wave_publish(am_r, dres_amax);
 __global__ U2PL_BN_KERNEL(4) void k_bn_bwd_apply(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
                                const float* __restrict__ y, long ldy, const float* __restrict__ mean,
                                const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -587,54 +724,20 @@ __global__ U2PL_BN_KERNEL(4) void k_bn_bwd_apply(const float* __restrict__ dy, l
                                float* __restrict__ dres, long lddr, long M, int C, const double* __restrict__ psums,
                                float* __restrict__ gsink, float* __restrict__ bsink, int accumulate,
                                unsigned* __restrict__ dx_amax, unsigned* __restrict__ dres_amax, const float* __restrict__ relu_beta) {
-    unsigned am_x = 0u, am_r = 0u;
-    if (psums && blockIdx.y == 0) {   // (u2pl_bn_bwd_apply_pg_f32) the parameter gradients ride along: k_sums_to_f32's arithmetic, dgamma = S1, dbeta = S0
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < C; i += (long)gridDim.x * blockDim.x) {
-            gsink[i] = (accumulate ? gsink[i] : 0.f) + (float)(psums[C + i] * (double)1.0f);
-            bsink[i] = (accumulate ? bsink[i] : 0.f) + (float)(psums[i] * (double)1.0f);
-        }
-    }
-    const ColOwner o = col_owner(C);
-    if (o.active) {
-        const int c = o.c;
-        const int mode = (sums ? 1 : 0) | (!y && relu_beta ? 2 : 0);
-        BnBwdCol k;
-        k.is = *(const float4*)(invstd + c); k.ga = *(const float4*)(gamma + c);
-        k.gi = f4mul(k.ga, k.is);
-        k.mu = mode ? *(const float4*)(mean + c) : f4zero();
-        k.be = (mode & 2) ? *(const float4*)(relu_beta + c) : f4zero();
-        k.m0 = f4zero(); k.m1 = f4zero();
-        if (sums) {
-            k.m0 = make_float4((float)(sums[c] / count), (float)(sums[c + 1] / count), (float)(sums[c + 2] / count),
-                               (float)(sums[c + 3] / count));
-            k.m1 = make_float4((float)(sums[C + c] / count), (float)(sums[C + c + 1] / count), (float)(sums[C + c + 2] / count),
-                               (float)(sums[C + c + 3] / count));
-        }
-        ImageOf<long> im;
-        im.init(drop != nullptr, o.r, o.step, o.chunk - BN_ROWS * o.step, rows_per_image);
-        const float* dropc = drop ? drop + c : nullptr;
-        const long sg = o.step * lddy, sx = o.step * ldx, sy = o.step * ldy, sdx = o.step * lddx, sdr = o.step * lddr;
-        const float* gp = dy + o.r * lddy + c;
-        const float* xp = x + o.r * ldx + c;
-        const float* yp = y ? y + o.r * ldy + c : nullptr;
-        float* dxp = dx + o.r * lddx + c;
-        float* drp = dres ? dres + o.r * lddr + c : nullptr;
-        for (long r = o.r; r < M; r += o.chunk) {
-            if (r + (BN_ROWS - 1) * o.step < M) {
-                bn_bwd_rows<BN_ROWS>(gp, sg, xp, sx, yp, sy, dxp, sdx, drp, sdr, dropc, C, im, mode, k, am_x, am_r);
-            } else {      // the last chunk of the tensor
-                for (int u = 0; r + u * o.step < M; ++u)
-                    bn_bwd_rows<1>(gp + u * sg, sg, xp + u * sx, sx, yp ? yp + u * sy : nullptr, sy, dxp + u * sdx, sdx,
-                                   drp ? drp + u * sdr : nullptr, sdr, dropc, C, im, mode, k, am_x, am_r);
-            }
-            im.jump();
-            gp += o.chunk * lddy; xp += o.chunk * ldx; dxp += o.chunk * lddx;
-            if (yp) yp += o.chunk * ldy;
-            if (drp) drp += o.chunk * lddr;
-        }
-    }
-    if (dx_amax) amax_wave_publish(am_x, dx_amax);
-    if (dres_amax) amax_wave_publish(am_r, dres_amax);
+    const unsigned* const bits = nullptr; const long ldb = 0;
+    U2PL_BN_BWD_APPLY_BODY(false)
+}
+// the ReLU mask from the forward's bit plane instead of y (C % 32 == 0)
+__global__ U2PL_BN_KERNEL(4) void k_bn_bwd_apply_bits(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
+                               const unsigned* __restrict__ bits, long ldb, const float* __restrict__ mean,
+                               const float* __restrict__ invstd, const float* __restrict__ gamma,
+                               const float* __restrict__ drop, long rows_per_image,
+                               const double* __restrict__ sums, double count, float* __restrict__ dx, long lddx,
+                               float* __restrict__ dres, long lddr, long M, int C, const double* __restrict__ psums,
+                               float* __restrict__ gsink, float* __restrict__ bsink, int accumulate,
+                               unsigned* __restrict__ dx_amax, unsigned* __restrict__ dres_amax) {
+    const float* const y = nullptr; const long ldy = 0; const float* const relu_beta = nullptr;
+    U2PL_BN_BWD_APPLY_BODY(true)
 }
 U2PL_API int u2pl_bn_bwd_apply_f32(const float* dy, long lddy, const float* x, long ldx, const float* y, long ldy,
                                    const float* mean, const float* invstd, const float* gamma, const float* drop,
@@ -672,6 +775,20 @@ U2PL_API int u2pl_bn_bwd_apply_amax_f32(const float* dy, long lddy, const float*
     U2PL_LAUNCH(k_bn_bwd_apply, bn_grid(M, C, 4), dim3(256), 0, stream, dy, lddy, x, ldx, y, ldy,
                        mean, invstd, gamma, drop, rows_per_image, sums, count, dx, lddx, dres, lddr, M, C, psums, gsink, bsink,
                        accumulate, (unsigned*)dx_amax, (unsigned*)dres_amax, relu_beta);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+// u2pl_bn_bwd_apply_amax_f32 with the ReLU mask from the forward's bit plane (u2pl_bn_apply_bits_f32) instead of y: train
+// (sums) and eval (sums == NULL), with and without dres, parameter gradients (psums) and maxima
+U2PL_API int u2pl_bn_bwd_apply_bits_f32(const float* dy, long lddy, const float* x, long ldx, const unsigned* bits, long ldb,
+                                        const float* mean, const float* invstd, const float* gamma, const float* drop,
+                                        long rows_per_image, const double* sums, double count, float* dx, long lddx,
+                                        float* dres, long lddr, long M, int C, const double* psums, float* gsink, float* bsink,
+                                        int accumulate, float* dx_amax, float* dres_amax, hipStream_t stream) {
+    if (C % 32 || !bits || ldb < C / 32 || (psums && (!gsink || !bsink))) return U2PL_EINVAL;
+    U2PL_LAUNCH(k_bn_bwd_apply_bits, bn_grid(M, C, 4), dim3(256), 0, stream, dy, lddy, x, ldx, bits, ldb,
+                       mean, invstd, gamma, drop, rows_per_image, sums, count, dx, lddx, dres, lddr, M, C, psums, gsink, bsink,
+                       accumulate, (unsigned*)dx_amax, (unsigned*)dres_amax);
     U2PL_LAUNCH_CHECK();
     return 0;
 }

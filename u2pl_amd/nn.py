@@ -661,26 +661,40 @@ def _bn_finalize(sums, count, mod):
     return mean, invstd
 
 
-def _bn_apply(x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, plain=False):
+def _act_with_mask_bits(N, C, H, W, device):
+    """-> y, bits: a new activation with room for its ReLU mask behind the last row -- int32 [M][C / 32], bit c % 32 of word
+    [row][c / 32] = y[row][c] > 0 -- in ONE buffer allocated like every activation: the apply entries find the plane from y
+    (relu = 3, include/u2pl_hip.h)"""
+    M = N * H * W
+    buf = torch.empty(M * C + M * (C // 32), dtype=torch.float32, device=device)
+    return buf[:M * C].view(N, H, W, C).permute(0, 3, 1, 2), buf[M * C:].view(torch.int32).view(M, C // 32)
+
+
+def _bn_apply(x, ldx, mean, invstd, gamma, beta, res, ldr, relu, drop, plain=False, mask_bits=False):
     """y = [drop *] [relu]((x - mean) * invstd * gamma + beta [+ res]) as a new activation.  With split-fp16 on, the launch
-    also leaves max |y| for the convolutions that read y; plain: not wanted (y is read by another apply only)"""
+    also leaves max |y| for the convolutions that read y; plain: not wanted (y is read by another apply only).
+    mask_bits (ReLU, C % 32 == 0): -> y, bits -- the launch also leaves [y > 0] as a bit plane (_act_with_mask_bits)"""
     N, C, H, W = x.shape
-    y = new_act(N, C, H, W, x.device)
+    y, bits = _act_with_mask_bits(N, C, H, W, x.device) if mask_bits else (new_act(N, C, H, W, x.device), None)
+    act = 3 if mask_bits else int(relu)
     if CONV_H["on"] and not plain:
         y_amax = amax_slot(x.device)
-        call("u2pl_bn_apply_amax_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, int(relu), drop, H * W, y, C, N * H * W, C, y_amax)
+        call("u2pl_bn_apply_amax_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, act, drop, H * W, y, C, N * H * W, C, y_amax)
         set_amax(y, y_amax)
     else:
-        call("u2pl_bn_apply_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, int(relu), drop, H * W, y, C, N * H * W, C)
-    return y
+        call("u2pl_bn_apply_f32", x, ldx, mean, invstd, gamma, beta, res, ldr, act, drop, H * W, y, C, N * H * W, C)
+    return (y, bits) if mask_bits else y
 
 
-def _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, out, gamma=None, rbeta=None):
+def _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, out, gamma=None, rbeta=None, bits=None):
     """LOCAL backward sums of one BatchNorm into out (double [2C]: dbeta, then dgamma).  The ReLU mask is [y > 0] (y None: no
-    ReLU) or -- rbeta, the layer's beta, given -- recomputed from x with the forward's own expression"""
+    ReLU), or -- rbeta, the layer's beta, given -- recomputed from x with the forward's own expression, or -- bits given -- read
+    from the forward's bit plane"""
     N, C, H, W = x.shape
     wsb = _ws(query("u2pl_colreduce_workspace_bytes", N * H * W, 1, C), gy.device)
-    if rbeta is not None:
+    if bits is not None:
+        call("u2pl_bn_bwd_sums_bits_f32", gy, ldg, x, ldx, bits, C // 32, mean, invstd, drop, H * W, N * H * W, C, wsb, out)
+    elif rbeta is not None:
         call("u2pl_bn_bwd_sums_mx_f32", gy, ldg, x, ldx, mean, invstd, gamma, rbeta, drop, H * W, N * H * W, C, wsb, out)
     else:
         call("u2pl_bn_bwd_sums_f32", gy, ldg, x, ldx, y, C, mean, invstd, drop, H * W, N * H * W, C, wsb, out)
@@ -703,23 +717,29 @@ def _param_grads(sums, C, gsink, bsink, need):
     return None, None
 
 
-def _bn_bwd_apply(gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums, count, with_dres=False, pg=None, rbeta=None, maxima=False):
+def _bn_bwd_apply(gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums, count, with_dres=False, pg=None, rbeta=None, maxima=False,
+                  bits=None):
     """-> dx, dres (the residual's gradient, when asked for) of one BatchNorm from the -- exchanged -- backward sums (None: eval
     mode).  The three entries launch one kernel, k_bn_bwd_apply.  pg = (psums, gsink, bsink): the launch also adds the
     parameter gradients, taken from the LOCAL sums psums, into the arena sinks.  rbeta: the ReLU mask from x (_bn_bwd_sums).
-    maxima: leave max |dx| / max |dres| for the data / weight gradients that read them (split-fp16)"""
+    maxima: leave max |dx| / max |dres| for the data / weight gradients that read them (split-fp16).  bits: the ReLU mask from
+    the forward's bit plane (one entry with every operand of the _amax one, k_bn_bwd_apply_bits)"""
     N, C, H, W = x.shape
     hw, M, dev = H * W, N * H * W, gy.device
     dx = new_act(N, C, H, W, dev)
     dres = new_act(N, C, H, W, dev) if with_dres else None
     psums, gsink, bsink = pg or (None, None, None)
     # the _amax entry is the only one with the maxima and the rbeta operands; it carries the parameter gradients too when asked
-    amax_entry = maxima or rbeta is not None
+    amax_entry = maxima or rbeta is not None or bits is not None
     if amax_entry:
         dx_amax = amax_slot(dev) if maxima else None
         dres_amax = amax_slot(dev) if (with_dres and maxima) else None
-        call("u2pl_bn_bwd_apply_amax_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, hw, sums, count, dx, C, dres, C, M, C,
-             psums, gsink, bsink, 1, dx_amax, dres_amax, rbeta)
+        if bits is not None:
+            call("u2pl_bn_bwd_apply_bits_f32", gy, ldg, x, ldx, bits, C // 32, mean, invstd, gamma, drop, hw, sums, count, dx, C,
+                 dres, C, M, C, psums, gsink, bsink, 1, dx_amax, dres_amax)
+        else:
+            call("u2pl_bn_bwd_apply_amax_f32", gy, ldg, x, ldx, y, C, mean, invstd, gamma, drop, hw, sums, count, dx, C, dres, C, M,
+                 C, psums, gsink, bsink, 1, dx_amax, dres_amax, rbeta)
         if dx_amax is not None:
             set_amax(dx, dx_amax)
         if dres_amax is not None:
@@ -739,7 +759,8 @@ class _BNFn(torch.autograd.Function):
     """one BatchNorm (+residual, ReLU, Dropout2d scale): single GPU, per-layer SyncBatchNorm exchange, eval mode"""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, res, drop, mod, relu, gsink, bsink, pre_sums=None, link=None):
+    def forward(ctx, x, gamma, beta, res, drop, mod, relu, gsink, bsink, pre_sums=None, link=None, record=False):
+        """record: the caller's grad mode (it is off in here, and needs_input_grad does not follow it)"""
         x, ldx = as_rows(x)
         N, C, H, W = x.shape
         ctx.link = link if res is not None else None
@@ -754,19 +775,26 @@ class _BNFn(torch.autograd.Function):
             mean, invstd = _bn_finalize(sums, count, mod)
         else:
             mean, invstd = mod.running_mean, _eval_invstd(mod, C, x.device)
-        y = _bn_apply(x, ldx, mean, invstd, gamma, beta, rr, ldr, relu, drop)
         # backward's ReLU mask: [y > 0] read from y, or -- no residual -- recomputed from x with the forward's own expression (same
-        # bits; y is then neither saved nor read: 4 of 12-16 bytes per element in each of the two backward passes)
+        # bits; y is then neither saved nor read: 4 of 12-16 bytes per element in each of the two backward passes), or -- with a
+        # residual, which the mask would need -- left by the apply launch as a bit plane that the backward reads in y's place
+        # (1/32 of y's bytes; only where a graph is recorded: a no_grad pass launches what it always did)
         ctx.mask_from_x = bool(relu and res is None and RELU_MASK_FROM_X and beta is not None)
-        ctx.save_for_backward(x, y if (relu and not ctx.mask_from_x) else None, mean, invstd, gamma, drop,
-                              beta if ctx.mask_from_x else None)
+        ctx.mask_bits = bool(relu and res is not None and RELU_MASK_BITS and C % 32 == 0 and record
+                             and any(ctx.needs_input_grad))
+        y = _bn_apply(x, ldx, mean, invstd, gamma, beta, rr, ldr, relu, drop, mask_bits=ctx.mask_bits)
+        bits = None
+        if ctx.mask_bits:
+            y, bits = y
+        ctx.save_for_backward(x, y if (relu and not ctx.mask_from_x and not ctx.mask_bits) else None, mean, invstd, gamma, drop,
+                              beta if ctx.mask_from_x else None, bits)
         ctx.meta = (ldx, mod.training, exchange, count, res is not None)
         ctx.gsink, ctx.bsink, ctx.group = gsink, bsink, mod.group
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, y, mean, invstd, gamma, drop, rbeta = ctx.saved_tensors
+        x, y, mean, invstd, gamma, drop, rbeta, bits = ctx.saved_tensors
         ldx, training, exchange, count, has_res = ctx.meta
         need_dx, need_pg, need_dres = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_res and ctx.needs_input_grad[3]
         if need_dres and not need_dx:
@@ -776,9 +804,9 @@ class _BNFn(torch.autograd.Function):
         C = x.shape[1]
         gy, ldg = as_rows(gy)
         sums = torch.empty(2 * C, dtype=torch.float64, device=gy.device)
-        _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, sums, gamma, rbeta)
+        _bn_bwd_sums(gy, ldg, x, ldx, y, mean, invstd, drop, sums, gamma, rbeta, bits)
         maxima = CONV_H["on"]                            # split-fp16: the convolutions that read dx / dres want their maxima
-        amax_entry = maxima or rbeta is not None         # what _bn_bwd_apply then launches
+        amax_entry = maxima or rbeta is not None or bits is not None         # what _bn_bwd_apply then launches
         # gradients into the arena: the two parameter-gradient writes ride in the apply launch (same arithmetic).  They are the
         # LOCAL sums, the apply needs the exchanged ones: under an exchange only the _amax entry takes the two apart (psums)
         pg_fused = FUSE_BN_FINISH and need_pg and ctx.gsink is not None and need_dx and (not exchange or amax_entry)
@@ -793,10 +821,10 @@ class _BNFn(torch.autograd.Function):
         dx = dres = None
         if need_dx:
             dx, dres = _bn_bwd_apply(gy, ldg, x, ldx, y, mean, invstd, gamma, drop, sums if training else None, count, need_dres,
-                                     pg, rbeta, maxima)
+                                     pg, rbeta, maxima, bits)
         if ctx.link is not None and dres is not None:
             dres = ctx.link.settle(dres)    # GradJoin: parked for the block's other consumer (conv1), or the total if it ran first
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
 
 
 # ---- packed SyncBatchNorm exchanges ------------------------------------------------------------------------------------
@@ -972,12 +1000,14 @@ class BatchNorm2d(nn.Module):
 
     def forward(self, x, res=None, relu=False, drop=None, pre_sums=None, res_link=None):
         return _BNFn.apply(x, self.weight, self.bias, res, drop, self, relu, _grad_sink(self.weight),
-                           _grad_sink(self.bias), pre_sums, res_link)
+                           _grad_sink(self.bias), pre_sums, res_link, torch.is_grad_enabled())
 
 
 FUSE_EVAL_BN = os.environ.get("U2PL_NO_EVAL_BN_FUSION") is None
 # round 6: a BatchNorm + ReLU without a residual recomputes its backward's ReLU mask from x instead of reading y (same bits)
 RELU_MASK_FROM_X = os.environ.get("U2PL_NO_RELU_MASK_FROM_X") is None
+# ... and, where there is a residual (a bottleneck's tail), from a bit plane that the forward apply leaves instead of from y
+RELU_MASK_BITS = os.environ.get("U2PL_NO_RELU_MASK_BITS") is None
 # round 5: fewer tiny launches on the conv -> statistics -> normalise chain (same arithmetic, same bits; U2PL_NO_BN_FINISH_FUSION=1:
 # the separate launches): finish + finalize in one, parameter gradients inside the backward apply, eval-mode invstd of a whole
 # model in one launch (eval_invstd)
