@@ -104,8 +104,7 @@ class _Act:
         return self.t.stride(0)
 
 
-def _out_size(n, k, stride, pad, dil):
-    return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
+_out_size = K._out_size
 
 
 def _pool_size(n):

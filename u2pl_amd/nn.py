@@ -11,6 +11,7 @@ GEMMs and state_dicts stay interchangeable with the reference.
 ``nn.Sequential`` containers are only *markers* (they keep the reference's
 Sequential indices); ``run_seq`` fuses them into the BatchNorm apply kernel.
 """
+import contextlib
 import math
 import os
 import weakref
@@ -36,14 +37,6 @@ from .operands import (AMAX_STATS, CONV_H, CONV_WS, PRESPLIT, WEIGHT_EPOCH, _AMA
 _WGRAD = {"stream": None, "enabled": os.environ.get("U2PL_NO_WGRAD_STREAM") is None}
 
 
-def _wgrad_stream():
-    if not _WGRAD["enabled"] or _lib.PROFILE is not None:
-        return None
-    if _WGRAD["stream"] is None:
-        _WGRAD["stream"] = torch.cuda.Stream()
-    return _WGRAD["stream"]
-
-
 def wgrad_stream_sync():
     _WGRAD["queued"] = False
     if _WGRAD["stream"] is not None:
@@ -51,11 +44,28 @@ def wgrad_stream_sync():
     _lib.SIDE_WORK.discard("wgrad")
 
 
-def _queue_wgrad_join():
-    """Join the side stream when the running backward pass finishes (once per pass)."""
-    if not _WGRAD.get("queued"):
+@contextlib.contextmanager
+def _wgrad_side(wanted, *operands):
+    """the fork of a backward function: inside the block the side stream is current and ordered behind the work queued on the
+    main stream so far; `operands` (None entries skipped) are the tensors the block reads.  Yields the stream, or None -- stream
+    off, or nothing `wanted` on it -- and the block runs on the main stream.  A caller that returns a result of the block to
+    autograd lets the main stream wait for the yielded stream after the block; everything else joins at the end of the pass"""
+    if not wanted or not _WGRAD["enabled"] or _lib.PROFILE is not None:
+        yield None
+        return
+    side = _WGRAD["stream"]
+    if side is None:
+        side = _WGRAD["stream"] = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    _lib.SIDE_WORK.add("wgrad")
+    for t_ in operands:
+        if t_ is not None:
+            t_.record_stream(side)
+    if not _WGRAD.get("queued"):      # join the side stream when the running backward pass finishes (once per pass)
         _WGRAD["queued"] = True
         torch.autograd.Variable._execution_engine.queue_callback(wgrad_stream_sync)
+    with torch.cuda.stream(side):
+        yield side
 
 
 def _grad_sink(p):
@@ -97,6 +107,53 @@ def wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W):
     return mt if gain >= CONV_ALGO["min_gain"] else 0
 
 
+def _out_size(n, k, stride, pad, dil):
+    """output extent of a convolution along one axis"""
+    return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def _check_weight_layout(weight, cin="Cin"):
+    R, S = weight.shape[2:]
+    if not weight.is_contiguous(memory_format=_CL) and not (R == 1 and S == 1 and weight.is_contiguous()):
+        raise HipError("conv weight must be stored channels_last ([Cout][R][S][%s])" % cin)
+
+
+def _ws_call(stem, src, head, planes, weight, *rest, h_tail=()):
+    """one GEMM on pre-split weight planes.  head: the operand's leading arguments (rows, pitch[, batch stride]) of `src`, the
+    tensor the producer handed over; planes: ws_forward / ws_dgrad / a ws_wino closure.  Split-fp16: stem_wsh_f32 with max |src|
+    behind `head`, the fp16 planes and h_tail (the bnact entries' output-maximum slot) at the end; else stem_ws_f32 on the bf16
+    planes.  Returns the operand's maximum (None in bf16 form)"""
+    if CONV_H["on"]:
+        amax = amax_of(src, head[0], head[1])
+        call(stem + "_wsh_f32", *head, amax, planes(weight, True), *rest, *h_tail)
+        return amax
+    call(stem + "_ws_f32", *head, planes(weight, False), *rest)
+    return None
+
+
+def _stem_patches(x, ldx, weight, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil):
+    """Cin % 32 != 0 (the 3-channel stem): -> col, wp, Kp -- the im2col patch matrix [N*Ho*Wo][Kp] and the weights as a
+    zero-padded [Cout][Kp] matrix, Kp = R*S*Cin rounded up to 32: the convolution is a pointwise one over `col`"""
+    Cout = weight.shape[0]
+    Kp = ((R * S * Cin + 31) // 32) * 32
+    col = torch.empty((N * Ho * Wo, Kp), dtype=torch.float32, device=x.device)
+    call("u2pl_im2col_f32", x, ldx, col, Kp, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil)
+    wp = torch.zeros((Cout, Kp), dtype=torch.float32, device=x.device)
+    wp[:, : R * S * Cin] = weight.permute(0, 2, 3, 1).reshape(Cout, R * S * Cin)
+    return col, wp, Kp
+
+
+def _wino_input(x, ldx, N, H, W, C, dil, mt, tiles, with_amax):
+    """-> V, v_amax: the Winograd-domain input; with_amax (split-fp16): the transform leaves max |V| as it writes (else None)"""
+    V = torch.empty((mt + 2) ** 2 * tiles * C, dtype=torch.float32, device=x.device)
+    if not with_amax:
+        call("u2pl_wino_input_f32", x, ldx, N, H, W, C, dil, mt, V)
+        return V, None
+    v_amax = amax_slot(x.device)
+    call("u2pl_wino_input_amax_f32", x, ldx, N, H, W, C, dil, mt, V, v_amax)
+    return V, v_amax
+
+
 def _wino_conv(x, ldx, weight, bias, y, N, H, W, Cin, Cout, dil, mt, transposed, pivot=None, epi=None, y_amax=None):
     """y <- conv3x3(x) in Winograd form; transposed: data-gradient (x = dY with Cout channels, y = dX with Cin).
     Returns the fused BatchNorm partial sums (or None).  epi = (mean, invstd, gamma, beta, res, ldr, relu): eval-mode
@@ -105,21 +162,15 @@ def _wino_conv(x, ldx, weight, bias, y, N, H, W, Cin, Cout, dil, mt, transposed,
     a2 = (mt + 2) ** 2
     Ci, Co = (Cout, Cin) if transposed else (Cin, Cout)
     tiles = query("u2pl_wino_tiles", N, H, W, dil, mt)
-    V = torch.empty(a2 * tiles * Ci, dtype=torch.float32, device=dev)
     ws = _ws_ok(Co, Ci) and weight.is_leaf
+    V, v_amax = _wino_input(x, ldx, N, H, W, Ci, dil, mt, tiles, ws and CONV_H["on"])
     Mb = torch.empty(a2 * tiles * Co, dtype=torch.float32, device=dev)
-    if ws and CONV_H["on"]:      # split-fp16: the transform leaves max |V| as it writes
-        v_amax = amax_slot(dev)
-        call("u2pl_wino_input_amax_f32", x, ldx, N, H, W, Ci, dil, mt, V, v_amax)
-        set_amax(V, v_amax)
-        call("u2pl_gemm_batched_wsh_f32", V, Ci, tiles * Ci, v_amax, ws_wino(weight, transposed, mt, True), Mb, Co, tiles * Co,
-             tiles, Ci, Co, a2)
-    elif ws:
-        call("u2pl_wino_input_f32", x, ldx, N, H, W, Ci, dil, mt, V)
-        call("u2pl_gemm_batched_ws_f32", V, Ci, tiles * Ci, ws_wino(weight, transposed, mt, False), Mb, Co, tiles * Co, tiles, Ci,
-             Co, a2)
+    if ws:
+        if v_amax is not None:
+            set_amax(V, v_amax)
+        _ws_call("u2pl_gemm_batched", V, (V, Ci, tiles * Ci), lambda w, h: ws_wino(w, transposed, mt, h), weight, Mb, Co, tiles * Co,
+                 tiles, Ci, Co, a2)
     else:
-        call("u2pl_wino_input_f32", x, ldx, N, H, W, Ci, dil, mt, V)
         U = torch.empty(a2 * Cout * Cin, dtype=torch.float32, device=dev)
         call("u2pl_wino_weight_f32", weight, Cout, Cin, int(transposed), mt, U)
         call("u2pl_gemm_batched_f32", V, Ci, tiles * Ci, U, Co * Ci, Mb, Co, tiles * Co, tiles, Ci, Co, a2)
@@ -146,10 +197,8 @@ class _ConvFn(torch.autograd.Function):
         x, ldx = as_rows(x)
         N, Cin, H, W = x.shape
         Cout, _, R, S = weight.shape
-        Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
-        Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
-        if not weight.is_contiguous(memory_format=_CL) and not (R == 1 and S == 1 and weight.is_contiguous()):
-            raise HipError("conv weight must be stored channels_last ([Cout][R][S][Cin])")
+        Ho, Wo = _out_size(H, R, stride, pad, dil), _out_size(W, S, stride, pad, dil)
+        _check_weight_layout(weight)
         # the second output (the fused BatchNorm sums) is not differentiable: without this autograd materialises a zero fp64
         # gradient for it in front of every backward call (116 fill launches per step, profiles/r05_bench_serial_kernel_stats.csv)
         ctx.set_materialize_grads(False)
@@ -162,19 +211,15 @@ class _ConvFn(torch.autograd.Function):
                   and H * W > 1)
         ctx.bf = use_bf
         sfx = "_bf16op_f32" if use_bf else "_f32"
+        geom = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
         if H * W == 1 and R == 1 and S == 1 and stride == 1 and pad == 0 and N <= 16 and Cin % 4 == 0:
             # image-pooling branch of the ASPP: float64-accumulated dense layer (see csrc/nn.hip:k_dense_small)
             call("u2pl_dense_small_f32", x, ldx, weight, bias, y, Cout, N, Cin, Cout)
             pivot = None if pivot is None else False   # statistics by the stand-alone pass
         elif Cin % 32:
-            Kp = ((R * S * Cin + 31) // 32) * 32
-            col = torch.empty((N * Ho * Wo, Kp), dtype=torch.float32, device=x.device)
-            call("u2pl_im2col_f32", x, ldx, col, Kp, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil)
-            wp = torch.zeros((Cout, Kp), dtype=torch.float32, device=x.device)
-            wp[:, : R * S * Cin] = weight.permute(0, 2, 3, 1).reshape(Cout, R * S * Cin)
+            col, wp, Kp = _stem_patches(x, ldx, weight, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil)
             call("u2pl_conv2d_fwd_f32", col, Kp, wp, bias, y, Cout, N, Ho, Wo, Kp, Ho, Wo, Cout, 1, 1, 1, 0, 1)
-        elif not use_bf and wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W):
-            mt = wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W)
+        elif not use_bf and (mt := wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W)):
             part, V = _wino_conv(x, ldx, weight, bias, y, N, H, W, Cin, Cout, dil, mt, False, pivot)
             if ctx.needs_input_grad[1]:
                 col = V     # the transformed input is the weight gradient's operand: keep it instead of redoing it
@@ -186,29 +231,17 @@ class _ConvFn(torch.autograd.Function):
             ws = not use_bf and _ws_ok(Cout, R * S * Cin)
             nblk = query("u2pl_igemm_ws_stat_blocks", N, Ho, Wo) if ws else query("u2pl_conv2d_fwd_stat_blocks", N, Ho, Wo, Cout)
             part = torch.empty((nblk, 2, Cout), dtype=torch.float32, device=x.device)
-            if ws and CONV_H["on"]:
-                ctx.x_amax = amax_of(x_in, x, ldx)
-                call("u2pl_conv2d_fwd_bnstats_wsh_f32", x, ldx, ctx.x_amax, ws_forward(weight, True), bias, y, Cout, N, H, W, Cin,
-                     Ho, Wo, Cout, R, S, stride, pad, dil, pivot, part)
-            elif ws:
-                call("u2pl_conv2d_fwd_bnstats_ws_f32", x, ldx, ws_forward(weight, False), bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout,
-                     R, S, stride, pad, dil, pivot, part)
+            if ws:
+                ctx.x_amax = _ws_call("u2pl_conv2d_fwd_bnstats", x_in, (x, ldx), ws_forward, weight, bias, y, Cout, *geom, pivot, part)
             else:
-                call("u2pl_conv2d_fwd_bnstats" + sfx, x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride,
-                     pad, dil, pivot, part)
+                call("u2pl_conv2d_fwd_bnstats" + sfx, x, ldx, weight, bias, y, Cout, *geom, pivot, part)
             sums = part          # raw partials, see above
         elif not use_bf and _ws_ok(Cout, R * S * Cin):
-            if CONV_H["on"]:
-                ctx.x_amax = amax_of(x_in, x, ldx)
-                call("u2pl_conv2d_fwd_wsh_f32", x, ldx, ctx.x_amax, ws_forward(weight, True), bias, y, Cout, N, H, W, Cin, Ho, Wo,
-                     Cout, R, S, stride, pad, dil)
-            else:
-                call("u2pl_conv2d_fwd_ws_f32", x, ldx, ws_forward(weight, False), bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S,
-                     stride, pad, dil)
+            ctx.x_amax = _ws_call("u2pl_conv2d_fwd", x_in, (x, ldx), ws_forward, weight, bias, y, Cout, *geom)
         else:
-            call("u2pl_conv2d_fwd" + sfx, x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
+            call("u2pl_conv2d_fwd" + sfx, x, ldx, weight, bias, y, Cout, *geom)
         ctx.save_for_backward(x, weight, col)
-        ctx.geom = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ldx)
+        ctx.geom = geom + (ldx,)
         ctx.has_bias = bias is not None
         ctx.wsink, ctx.bsink = wsink, bsink
         if pivot is not None:
@@ -228,158 +261,149 @@ class _ConvFn(torch.autograd.Function):
         gy, ldg = as_rows(gy)
         dev = gy.device
         M = N * Ho * Wo
-        Cp = Cout
+        Cp, weight_k = Cout, weight
         if Cout % 32:  # narrow heads (num_classes outputs): zero-pad the gradient columns once
             Cp = (Cout + 31) // 32 * 32
             gp = torch.zeros((M, Cp), dtype=torch.float32, device=dev)
             call("u2pl_copy_cols_f32", gy, ldg, gp, Cp, M, Cout)
             gy, ldg = gp, Cp
-            wpad = torch.zeros((Cp, Cin, R, S), dtype=torch.float32, device=dev).contiguous(memory_format=_CL)
-            wpad[:Cout] = weight
-            weight_k = wpad
-        else:
-            weight_k = weight
+            weight_k = torch.zeros((Cp, Cin, R, S), dtype=torch.float32, device=dev).contiguous(memory_format=_CL)
+            weight_k[:Cout] = weight
         dx = dw = db = None
         # what the OTHER consumers of this conv's input have contributed to its gradient so far (GradJoin): folded into this
         # launch where a fused form exists, added in place otherwise; handed on or returned by join.settle below
         join = ctx.link
-        prev = join.acc if join is not None else None
         if join is not None and not ctx.needs_input_grad[0]:
             raise HipError("gradient join on a convolution whose input needs no gradient")
         if ctx.needs_input_grad[0]:
-            dx = new_act(N, Cin, H, W, dev)
-            included = prev is None
-            epi = None
-            if prev is not None and Cin % 4 == 0:
-                one, zero = _identity_bn(Cin, dev)
-                rr, ldr = as_rows(prev)
-                epi = (zero, one, one, zero, rr, ldr, 0)     # identity BatchNorm + `res` = the running sum: (v - 0) * 1 * 1 + 0 + res
-            mt = wino_tile(Cp, Cin, R, S, stride, pad, dil, H, W) if (Cp == Cout and not ctx.bf) else 0
-            if mt:   # data gradient = the same convolution with rotated taps and swapped channel roles
-                _wino_conv(gy, ldg, weight_k, None, dx, N, H, W, Cin, Cout, dil, mt, True, None, epi)
-                included = included or epi is not None     # (the output transform's residual epilogue)
-            elif (epi is not None and R == 1 and S == 1 and stride == 1 and pad == 0 and Cp == Cout and not ctx.bf
-                  and _ws_ok(Cin, Cout)):
-                # pointwise: the data gradient IS a pointwise forward convolution with the transposed weight planes -- run it
-                # through the forward kernel's eval-BatchNorm epilogue with identity parameters and the running sum as its
-                # `res`: dx = (gy . W) + prev in ONE pass instead of the GEMM + autograd's elementwise add over the 4x-wide
-                # block input (46 adds, 3.2 ms per step before round 5)
-                if CONV_H["on"]:
-                    call("u2pl_conv2d_fwd_bnact_wsh_f32", gy, ldg, amax_of(gy_in, gy, ldg), ws_dgrad(weight, True), None, dx, Cin, N,
-                         H, W, Cout, H, W, Cin, 1, 1, 1, 0, 1, *epi, None)
-                else:
-                    call("u2pl_conv2d_fwd_bnact_ws_f32", gy, ldg, ws_dgrad(weight, False), None, dx, Cin, N, H, W, Cout, H, W, Cin, 1, 1,
-                         1, 0, 1, *epi)
-                included = True
-            elif Cp == Cout and not ctx.bf and _ws_ok(Cin, R * S * Cout):
-                if CONV_H["on"]:
-                    call("u2pl_conv2d_dgrad_wsh_f32", gy, ldg, amax_of(gy_in, gy, ldg), ws_dgrad(weight, True), dx, Cin, N, H, W, Cin,
-                         Ho, Wo, Cout, R, S, stride, pad, dil)
-                else:
-                    call("u2pl_conv2d_dgrad_ws_f32", gy, ldg, ws_dgrad(weight, False), dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S,
-                         stride, pad, dil)
-            else:
-                wT = torch.empty(Cin * R * S * Cp, dtype=torch.float32, device=dev)
-                call("u2pl_weight_transpose_f32", weight_k, wT, Cp, R * S, Cin)
-                call("u2pl_conv2d_dgrad_bf16op_f32" if ctx.bf else "u2pl_conv2d_dgrad_f32", gy, ldg, wT, dx, Cin, N, H, W, Cin,
-                     Ho, Wo, Cp, R, S, stride, pad, dil)
+            dx, included = _conv_dgrad(ctx, gy_in, gy, ldg, weight, weight_k, Cp, join.acc if join is not None else None)
             if join is not None:
                 dx = join.settle(dx, included)      # None unless this was the last consumer to report
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        wg_mt = (wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W)
+                 if need_w and Cp == Cout and not ctx.bf and CONV_ALGO.get("wgrad", 1) else 0)     # Winograd weight gradient
         # split-fp16 weight gradients (k_wgrad_tr only): the operands' maxima are taken on THIS stream, before the side stream forks
-        wg_h = (CONV_H["on"] and ctx.needs_input_grad[1] and Cp == Cout and not ctx.bf and Cin % 32 == 0
+        wg_h = (CONV_H["on"] and need_w and Cp == Cout and not ctx.bf and Cin % 32 == 0
                 and query("u2pl_wgrad_h_eligible", Cin, Cout) == 1)
-        wg_wino = wg_h and bool(CONV_ALGO.get("wgrad", 1) and wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W))
         gy_amax = x_amax = None
-        if wg_h and not wg_wino:
+        if wg_h and not wg_mt:
             gy_amax = amax_of(gy_in, gy, ldg)
             x_amax = ctx.x_amax if ctx.x_amax is not None else amax_of(x, x, ldx)
-        side = _wgrad_stream() if (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            _lib.SIDE_WORK.add("wgrad")
-            for t_ in (gy, x, col, gy_amax, x_amax, ctx.col_amax):
-                if t_ is not None:
-                    t_.record_stream(side)
-            _queue_wgrad_join()
-            stream_ctx = torch.cuda.stream(side)
-            stream_ctx.__enter__()
-        if ctx.needs_input_grad[1]:
-            sink = ctx.wsink
-            if Cin % 32:  # 3-channel stem (col = im2col patches): gradient of the padded [Cout][Kp] patch-matrix weights
-                Kp = col.shape[1]
-                tmp = torch.empty((Cp, Kp), dtype=torch.float32, device=dev)
-                wsb = _ws(query("u2pl_conv2d_wgrad_workspace_bytes", N, Ho, Wo, Kp, Cp, 1, 1), dev)
-                call("u2pl_conv2d_wgrad_f32", gy, ldg, col, Kp, tmp, wsb, 0, N, Ho, Wo, Kp, Ho, Wo, Cp, 1, 1, 1, 0, 1)
-                g = tmp[:Cout, : R * S * Cin].reshape(Cout, R, S, Cin).permute(0, 3, 1, 2)
-                if sink is not None:
-                    sink.add_(g)
-                else:
-                    dw = g.contiguous(memory_format=_CL)
-            elif Cp == Cout and not ctx.bf and CONV_ALGO.get("wgrad", 1) and wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W):
-                # Winograd weight gradient: dU = sum_tiles (A dY A^T) (x) (B^T x B), dW = G^T dU G
-                mt = wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W)
-                a2 = (mt + 2) ** 2
-                tiles = query("u2pl_wino_tiles", N, H, W, dil, mt)
-                V, v_amax = col, ctx.col_amax      # saved by the forward
-                if V is None:
-                    V = torch.empty(a2 * tiles * Cin, dtype=torch.float32, device=dev)
-                    if wg_h:
-                        v_amax = amax_slot(dev)
-                        call("u2pl_wino_input_amax_f32", x, ldx, N, H, W, Cin, dil, mt, V, v_amax)
-                    else:
-                        call("u2pl_wino_input_f32", x, ldx, N, H, W, Cin, dil, mt, V)
-                Mg = torch.empty(a2 * tiles * Cout, dtype=torch.float32, device=dev)
-                ns = query("u2pl_wgrad_batched_splits", tiles, Cin, Cout, a2)
-                part = torch.empty(ns * Cout * a2 * Cin, dtype=torch.float32, device=dev)
-                if wg_h:
-                    if v_amax is None:
-                        v_amax = amax_slot(dev)
-                        call("u2pl_absmax_f32", V, Cin, a2 * tiles, Cin, v_amax, 0)
-                    mg_amax = amax_slot(dev)
-                    call("u2pl_wino_gy_amax_f32", gy, ldg, N, H, W, Cout, dil, mt, Mg, mg_amax)
-                    call("u2pl_wgrad_batched_h_f32", Mg, Cout, tiles * Cout, mg_amax, V, Cin, tiles * Cin, v_amax, part, tiles, Cin,
-                         Cout, a2)
-                else:
-                    call("u2pl_wino_gy_f32", gy, ldg, N, H, W, Cout, dil, mt, Mg)
-                    call("u2pl_wgrad_batched_f32", Mg, Cout, tiles * Cout, V, Cin, tiles * Cin, part, tiles, Cin, Cout, a2)
-                tgt = sink if sink is not None else torch.empty_like(weight)
-                call("u2pl_wino_wgrad_finish_f32", part, ns, Cout, Cin, mt, int(sink is not None), tgt)
-                if sink is None:
-                    dw = tgt
-            else:
-                wsb = _ws(query("u2pl_conv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cp, R, S), dev)
-                direct = sink is not None and Cp == Cout
-                tgt = sink if direct else torch.empty_like(weight_k)
-                if gy_amax is not None:
-                    call("u2pl_conv2d_wgrad_h_f32", gy, ldg, gy_amax, x, ldx, x_amax, tgt, wsb, int(direct), N, H, W, Cin, Ho, Wo,
-                         Cp, R, S, stride, pad, dil)
-                else:
-                    call("u2pl_conv2d_wgrad_bf16op_f32" if ctx.bf else "u2pl_conv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb,
-                         int(direct), N, H, W, Cin, Ho, Wo, Cp, R, S, stride, pad, dil)
-                if not direct:
-                    if sink is not None:
-                        sink.add_(tgt[:Cout])
-                    else:
-                        dw = tgt[:Cout] if Cp != Cout else tgt
-        if ctx.needs_input_grad[1]:
-            _mark_ready(ctx.wsink)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            sums = torch.empty(2 * Cp, dtype=torch.float64, device=dev)
-            wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, Cp), dev)
-            call("u2pl_colsum_f32", gy, ldg, M, 1, Cp, wsb, sums)
-            if ctx.bsink is not None:
-                call("u2pl_sums_to_f32", sums, Cout, 1.0, 1, ctx.bsink)
-                _mark_ready(ctx.bsink)
-            else:
-                db = torch.empty(Cout, dtype=torch.float32, device=dev)
-                call("u2pl_sums_to_f32", sums, Cout, 1.0, 0, db)
-        if side is not None:
-            stream_ctx.__exit__(None, None, None)
-            for t_ in (dw, db):
-                if t_ is not None:   # returned to autograd on the main stream
-                    torch.cuda.current_stream().wait_stream(side)
-                    break
+        with _wgrad_side(need_w or need_b, gy, x, col, gy_amax, x_amax, ctx.col_amax) as side:
+            if need_w:
+                dw = _conv_wgrad(ctx, gy, ldg, x, weight, weight_k, col, Cp, wg_mt, wg_h, gy_amax, x_amax)
+                _mark_ready(ctx.wsink)
+            if need_b:
+                db = _bias_grad(gy, ldg, M, Cp, Cout, ctx.bsink)
+        if side is not None and (dw is not None or db is not None):      # returned to autograd on the main stream
+            torch.cuda.current_stream().wait_stream(side)
         return dx, dw, db, None, None, None, None, None, None, None, None
+
+
+def _conv_dgrad(ctx, gy_in, gy, ldg, weight, weight_k, Cp, prev):
+    """data gradient of _ConvFn -> dx, included: whether dx already contains `prev`, the running sum of the input's GradJoin.
+    gy / weight_k: the gradient rows and the weight as the kernels read them (zero-padded to Cp columns for a narrow head)"""
+    N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, _ = ctx.geom
+    dev = gy.device
+    dx = new_act(N, Cin, H, W, dev)
+    included = prev is None
+    epi = None
+    if prev is not None and Cin % 4 == 0:
+        one, zero = _identity_bn(Cin, dev)
+        rr, ldr = as_rows(prev)
+        epi = (zero, one, one, zero, rr, ldr, 0)     # identity BatchNorm + `res` = the running sum: (v - 0) * 1 * 1 + 0 + res
+    mt = wino_tile(Cp, Cin, R, S, stride, pad, dil, H, W) if (Cp == Cout and not ctx.bf) else 0
+    if mt:   # data gradient = the same convolution with rotated taps and swapped channel roles
+        _wino_conv(gy, ldg, weight_k, None, dx, N, H, W, Cin, Cout, dil, mt, True, None, epi)
+        included = included or epi is not None     # (the output transform's residual epilogue)
+    elif (epi is not None and R == 1 and S == 1 and stride == 1 and pad == 0 and Cp == Cout and not ctx.bf
+          and _ws_ok(Cin, Cout)):
+        # pointwise: the data gradient IS a pointwise forward convolution with the transposed weight planes -- run it
+        # through the forward kernel's eval-BatchNorm epilogue with identity parameters and the running sum as its
+        # `res`: dx = (gy . W) + prev in ONE pass instead of the GEMM + autograd's elementwise add over the 4x-wide
+        # block input (46 adds, 3.2 ms per step before round 5)
+        _ws_call("u2pl_conv2d_fwd_bnact", gy_in, (gy, ldg), ws_dgrad, weight, None, dx, Cin, N, H, W, Cout, H, W, Cin, 1, 1, 1, 0, 1,
+                 *epi, h_tail=(None,))
+        included = True
+    elif Cp == Cout and not ctx.bf and _ws_ok(Cin, R * S * Cout):
+        _ws_call("u2pl_conv2d_dgrad", gy_in, (gy, ldg), ws_dgrad, weight, dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
+    else:
+        wT = torch.empty(Cin * R * S * Cp, dtype=torch.float32, device=dev)
+        call("u2pl_weight_transpose_f32", weight_k, wT, Cp, R * S, Cin)
+        call("u2pl_conv2d_dgrad_bf16op_f32" if ctx.bf else "u2pl_conv2d_dgrad_f32", gy, ldg, wT, dx, Cin, N, H, W, Cin,
+             Ho, Wo, Cp, R, S, stride, pad, dil)
+    return dx, included
+
+
+def _conv_wgrad(ctx, gy, ldg, x, weight, weight_k, col, Cp, mt, wg_h, gy_amax, x_amax):
+    """weight gradient of _ConvFn, added into ctx.wsink (-> None) or returned.  mt: Winograd tile of the gradient (0: direct);
+    wg_h: split-fp16 form, with gy_amax / x_amax the direct kernel's operand maxima (taken by the caller)"""
+    N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ldx = ctx.geom
+    dev = gy.device
+    sink = ctx.wsink
+    if Cin % 32:  # 3-channel stem (col = im2col patches): gradient of the padded [Cout][Kp] patch-matrix weights
+        Kp = col.shape[1]
+        tmp = torch.empty((Cp, Kp), dtype=torch.float32, device=dev)
+        wsb = _ws(query("u2pl_conv2d_wgrad_workspace_bytes", N, Ho, Wo, Kp, Cp, 1, 1), dev)
+        call("u2pl_conv2d_wgrad_f32", gy, ldg, col, Kp, tmp, wsb, 0, N, Ho, Wo, Kp, Ho, Wo, Cp, 1, 1, 1, 0, 1)
+        g = tmp[:Cout, : R * S * Cin].reshape(Cout, R, S, Cin).permute(0, 3, 1, 2)
+        if sink is not None:
+            sink.add_(g)
+            return None
+        return g.contiguous(memory_format=_CL)
+    if mt:
+        # Winograd weight gradient: dU = sum_tiles (A dY A^T) (x) (B^T x B), dW = G^T dU G
+        a2 = (mt + 2) ** 2
+        tiles = query("u2pl_wino_tiles", N, H, W, dil, mt)
+        V, v_amax = col, ctx.col_amax      # saved by the forward
+        if V is None:
+            V, v_amax = _wino_input(x, ldx, N, H, W, Cin, dil, mt, tiles, wg_h)
+        Mg = torch.empty(a2 * tiles * Cout, dtype=torch.float32, device=dev)
+        ns = query("u2pl_wgrad_batched_splits", tiles, Cin, Cout, a2)
+        part = torch.empty(ns * Cout * a2 * Cin, dtype=torch.float32, device=dev)
+        if wg_h:
+            if v_amax is None:
+                v_amax = amax_slot(dev)
+                call("u2pl_absmax_f32", V, Cin, a2 * tiles, Cin, v_amax, 0)
+            mg_amax = amax_slot(dev)
+            call("u2pl_wino_gy_amax_f32", gy, ldg, N, H, W, Cout, dil, mt, Mg, mg_amax)
+            call("u2pl_wgrad_batched_h_f32", Mg, Cout, tiles * Cout, mg_amax, V, Cin, tiles * Cin, v_amax, part, tiles, Cin,
+                 Cout, a2)
+        else:
+            call("u2pl_wino_gy_f32", gy, ldg, N, H, W, Cout, dil, mt, Mg)
+            call("u2pl_wgrad_batched_f32", Mg, Cout, tiles * Cout, V, Cin, tiles * Cin, part, tiles, Cin, Cout, a2)
+        tgt = sink if sink is not None else torch.empty_like(weight)
+        call("u2pl_wino_wgrad_finish_f32", part, ns, Cout, Cin, mt, int(sink is not None), tgt)
+        return tgt if sink is None else None
+    wsb = _ws(query("u2pl_conv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cp, R, S), dev)
+    direct = sink is not None and Cp == Cout
+    tgt = sink if direct else torch.empty_like(weight_k)
+    if gy_amax is not None:
+        call("u2pl_conv2d_wgrad_h_f32", gy, ldg, gy_amax, x, ldx, x_amax, tgt, wsb, int(direct), N, H, W, Cin, Ho, Wo,
+             Cp, R, S, stride, pad, dil)
+    else:
+        call("u2pl_conv2d_wgrad_bf16op_f32" if ctx.bf else "u2pl_conv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb,
+             int(direct), N, H, W, Cin, Ho, Wo, Cp, R, S, stride, pad, dil)
+    if direct:
+        return None
+    if sink is not None:
+        sink.add_(tgt[:Cout])
+        return None
+    return tgt[:Cout] if Cp != Cout else tgt
+
+
+def _bias_grad(gy, ldg, M, Cp, Cout, bsink):
+    """bias gradient = the column sums of the Cp-wide gradient rows, first Cout of them: added into bsink (-> None) or returned"""
+    sums = torch.empty(2 * Cp, dtype=torch.float64, device=gy.device)
+    wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, Cp), gy.device)
+    call("u2pl_colsum_f32", gy, ldg, M, 1, Cp, wsb, sums)
+    if bsink is not None:
+        call("u2pl_sums_to_f32", sums, Cout, 1.0, 1, bsink)
+        _mark_ready(bsink)
+        return None
+    db = torch.empty(Cout, dtype=torch.float32, device=gy.device)
+    call("u2pl_sums_to_f32", sums, Cout, 1.0, 0, db)
+    return db
 
 
 _IDENT_BN = {}
@@ -495,10 +519,8 @@ class _GroupedConvFn(torch.autograd.Function):
             why = "weight has %d input channels per group, the input %d channels in %d groups" % (cig, Cin, groups)
         if why is not None:
             raise HipError("grouped convolution: " + why)
-        if not weight.is_contiguous(memory_format=_CL) and not (R == 1 and S == 1 and weight.is_contiguous()):
-            raise HipError("conv weight must be stored channels_last ([Cout][R][S][Cin/groups])")
-        Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
-        Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+        _check_weight_layout(weight, "Cin/groups")
+        Ho, Wo = _out_size(H, R, stride, pad, dil), _out_size(W, S, stride, pad, dil)
         ctx.set_materialize_grads(False)
         ctx.link = link
         y = new_act(N, Cout, Ho, Wo, x.device)
@@ -517,7 +539,6 @@ class _GroupedConvFn(torch.autograd.Function):
         N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups, ldx = ctx.geom
         gy, ldg = as_rows(gy)
         dev = gy.device
-        M = N * Ho * Wo
         dx = dw = db = None
         join = ctx.link
         if join is not None and not ctx.needs_input_grad[0]:
@@ -527,38 +548,21 @@ class _GroupedConvFn(torch.autograd.Function):
             call("u2pl_gconv2d_dgrad_f32", gy, ldg, weight, dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
             if join is not None:
                 dx = join.settle(dx, False)         # (no fused accumulate form: the running sum is added in place)
-        side = _wgrad_stream() if (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            _lib.SIDE_WORK.add("wgrad")
-            gy.record_stream(side)
-            x.record_stream(side)
-            _queue_wgrad_join()
-            stream_ctx = torch.cuda.stream(side)
-            stream_ctx.__enter__()
-        if ctx.needs_input_grad[1]:
-            sink = ctx.wsink
-            wsb = _ws(query("u2pl_gconv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups), dev)
-            tgt = sink if sink is not None else torch.empty_like(weight)
-            call("u2pl_gconv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb, int(sink is not None), N, H, W, Cin, Ho, Wo, Cout, R, S, stride,
-                 pad, dil, groups)
-            if sink is None:
-                dw = tgt
-            _mark_ready(sink)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            wsb = _ws(query("u2pl_colreduce_workspace_bytes", M, 1, Cout), dev)
-            call("u2pl_colsum_f32", gy, ldg, M, 1, Cout, wsb, sums)
-            if ctx.bsink is not None:
-                call("u2pl_sums_to_f32", sums, Cout, 1.0, 1, ctx.bsink)
-                _mark_ready(ctx.bsink)
-            else:
-                db = torch.empty(Cout, dtype=torch.float32, device=dev)
-                call("u2pl_sums_to_f32", sums, Cout, 1.0, 0, db)
-        if side is not None:
-            stream_ctx.__exit__(None, None, None)
-            if dw is not None or db is not None:    # returned to autograd on the main stream
-                torch.cuda.current_stream().wait_stream(side)
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        with _wgrad_side(need_w or need_b, gy, x) as side:
+            if need_w:
+                sink = ctx.wsink
+                wsb = _ws(query("u2pl_gconv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups), dev)
+                tgt = sink if sink is not None else torch.empty_like(weight)
+                call("u2pl_gconv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb, int(sink is not None), N, H, W, Cin, Ho, Wo, Cout, R, S,
+                     stride, pad, dil, groups)
+                if sink is None:
+                    dw = tgt
+                _mark_ready(sink)
+            if need_b:
+                db = _bias_grad(gy, ldg, N * Ho * Wo, Cout, Cout, ctx.bsink)
+        if side is not None and (dw is not None or db is not None):      # returned to autograd on the main stream
+            torch.cuda.current_stream().wait_stream(side)
         return dx, dw, db, None, None, None, None, None, None, None
 
 
@@ -1087,37 +1091,28 @@ def conv_bn_eval(conv, bn, x, res=None, relu=False):
     stride, pad, dil = conv.stride, conv.padding, conv.dilation
     if H * W == 1 or Cout % 4:
         return None
-    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+    Ho, Wo = _out_size(H, R, stride, pad, dil), _out_size(W, S, stride, pad, dil)
     dev = x.device
     invstd = _eval_invstd(bn, Cout, dev)
     rr, ldr = (None, 0) if res is None else as_rows(res)
     epi = (bn.running_mean, invstd, bn.weight, bn.bias, rr, ldr, int(relu))
     y = new_act(N, Cout, Ho, Wo, dev)
+    geom = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
     if Cin % 32:
-        Kp = ((R * S * Cin + 31) // 32) * 32
-        col = torch.empty((N * Ho * Wo, Kp), dtype=torch.float32, device=dev)
-        call("u2pl_im2col_f32", x, ldx, col, Kp, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil)
-        wp = torch.zeros((Cout, Kp), dtype=torch.float32, device=dev)
-        wp[:, : R * S * Cin] = weight.permute(0, 2, 3, 1).reshape(Cout, R * S * Cin)
+        col, wp, Kp = _stem_patches(x, ldx, weight, N, H, W, Cin, Ho, Wo, R, S, stride, pad, dil)
         call("u2pl_conv2d_fwd_bnact_f32", col, Kp, wp, bias, y, Cout, N, Ho, Wo, Kp, Ho, Wo, Cout, 1, 1, 1, 0, 1, *epi)
-    elif wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W):
+    elif mt := wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W):
         y_amax = amax_slot(dev) if CONV_H["on"] else None
-        _wino_conv(x, ldx, weight, bias, y, N, H, W, Cin, Cout, dil, wino_tile(Cin, Cout, R, S, stride, pad, dil, H, W),
-                   False, None, epi, y_amax)
+        _wino_conv(x, ldx, weight, bias, y, N, H, W, Cin, Cout, dil, mt, False, None, epi, y_amax)
         if y_amax is not None:
             set_amax(y, y_amax)
-    elif _ws_ok(Cout, R * S * Cin) and CONV_H["on"]:
-        y_amax = amax_slot(dev)
-        call("u2pl_conv2d_fwd_bnact_wsh_f32", x, ldx, amax_of(x_in, x, ldx), ws_forward(weight, True), bias, y, Cout, N, H, W, Cin, Ho,
-             Wo, Cout, R, S, stride, pad, dil, *epi, y_amax)
-        set_amax(y, y_amax)
     elif _ws_ok(Cout, R * S * Cin):
-        call("u2pl_conv2d_fwd_bnact_ws_f32", x, ldx, ws_forward(weight, False), bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S,
-             stride, pad, dil, *epi)
+        y_amax = amax_slot(dev) if CONV_H["on"] else None
+        _ws_call("u2pl_conv2d_fwd_bnact", x_in, (x, ldx), ws_forward, weight, bias, y, Cout, *geom, *epi, h_tail=(y_amax,))
+        if y_amax is not None:
+            set_amax(y, y_amax)
     else:
-        call("u2pl_conv2d_fwd_bnact_f32", x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil,
-             *epi)
+        call("u2pl_conv2d_fwd_bnact_f32", x, ldx, weight, bias, y, Cout, *geom, *epi)
     return y
 
 
