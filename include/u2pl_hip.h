@@ -547,10 +547,14 @@ int u2pl_sgd_step_f32(float* p, const float* g, float* buf, long n, long b1, lon
                       float momentum, float weight_decay, int first, float grad_scale, hipStream_t stream);
 int u2pl_ema_update_f32(float* t, const float* s, long n, float decay, float one_minus_decay, hipStream_t stream);
 /* torch.optim.Adam step (lr_helper.py:20-21; amsgrad off) on the same arena layout: bias_correction1 = 1 - beta1^t,
- * bias_correction2_sqrt = sqrt(1 - beta2^t) for the step count t kept by the host */
+ * bias_correction2_sqrt = sqrt(1 - beta2^t) for the step count t kept by the host.  one_minus_beta1 / one_minus_beta2 are
+ * the host's (float)(1.0 - (double)beta), rounded once as torch's scalar weights are (like one_minus_decay above): the
+ * device never forms 1.0f - beta, which at beta2 = 0.999 is 0.0009999871 instead of float(0.001).  beta1 is part of the call
+ * for the record of the hyper-parameters only: exp_avg is updated as m += one_minus_beta1 * (g - m) */
 int u2pl_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, long b1, long b2, float lr0,
-                       float lr1, float lr2, float beta1, float beta2, float eps, float weight_decay,
-                       float bias_correction1, float bias_correction2_sqrt, float grad_scale, hipStream_t stream);
+                       float lr1, float lr2, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                       float eps, float weight_decay, float bias_correction1, float bias_correction2_sqrt,
+                       float grad_scale, hipStream_t stream);
 /* The whole reliability split in ONE persistent launch (csrc/relfused.hip): bilinear up-sampling + entropy of the
  * train-mode teacher logits (train_semi.py:371-374,402), exact np.percentile thresholds (loss_helper.py:38-40,
  * train_semi.py:405-415), unsup target overwrite (loss_helper.py:41-43), low / high masks + nearest down-sampling +

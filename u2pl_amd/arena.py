@@ -182,8 +182,8 @@ class ParamArena:
         bc2s = math.sqrt(1.0 - betas[1] ** self.steps)
         bump_weight_epoch(self)
         call("u2pl_adam_step_f32", self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.n, b[0], b[1], float(lr[0]),
-             float(lr[1]), float(lr[2]), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(bc1),
-             float(bc2s), float(grad_scale))
+             float(lr[1]), float(lr[2]), float(betas[0]), 1.0 - float(betas[0]), float(betas[1]), 1.0 - float(betas[1]),
+             float(eps), float(weight_decay), float(bc1), float(bc2s), float(grad_scale))     # 1 - beta: double, rounded once
         presplit(self.params, self)
 
     def adam_views(self, p):
