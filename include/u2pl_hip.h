@@ -330,21 +330,19 @@ int u2pl_gconv2d_wgrad_f32(const float* dy, long lddy, const float* x, long ldx,
                            int accumulate, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
                            int S, int stride, int pad, int dil, int groups, hipStream_t stream);
 
-/* ---- igemm_ws.hip (split-fp32 implicit GEMM with pre-split weights; round 4) -------------------------------------
+/* ---- operands.hip (the GEMM operands derived from the weights: piece planes, their maxima, activation maxima) ----------
  * The weights of the network change once per optimizer step (train_semi.py:526-528 optimizer.step(), :531-548 the EMA
  * teacher), the convolutions read them ~14 times per step (resnet.py:120-140 through the two student and two teacher
- * passes and the backward).  u2pl_weight_split3_f32 splits a row-major fp32 matrix [rows][K] (K % 32 == 0) ONCE into the
- * three bf16 piece planes of the split-fp32 arithmetic, stored chunk-major in the image the GEMM's LDS tile has; the
- * *_ws entry points are the conv.hip calls of the same name with that buffer in place of the fp32 weight pointer:
+ * passes and the backward).  u2pl_weight_split3_f32 splits `batch` row-major fp32 matrices [rows][K] (K % 32 == 0, zw = rows * K
+ * floats apart) ONCE into the three bf16 piece planes of the split-fp32 arithmetic, stored chunk-major in the image the GEMM's
+ * LDS tile has: [K/32][3][Np][32] per matrix, the 16-byte segments of a row XOR-swizzled by (row >> 2) & 3 (csrc/ws_planes.h).
+ * The matrices the GEMMs read:
  *   forward:        the [Cout][R*S*Cin] matrix (the weight itself, channels_last)
  *   data gradient:  the transposed [Cin][R*S*Cout] matrix (u2pl_weight_transpose_f32)
- *   Winograd:       the batch of a*a component matrices U[a*a][O][C] of u2pl_wino_weight_f32 (batch = a*a)
- * Same arithmetic, same summation order as conv.hip's split kernels: results are bit-identical to u2pl_conv2d_fwd_f32 /
- * _bnstats / _bnact / u2pl_conv2d_dgrad_f32 / u2pl_gemm_batched_f32 under U2PL_CONV_SPLIT=1 (statistics partial sums
- * included; stats_partial has u2pl_igemm_ws_stat_blocks rows).  Cout > 64 only (narrower layers stay on conv.hip). */
+ *   Winograd:       the batch of a*a component matrices U[a*a][O][C] of u2pl_wino_weight_f32 (batch = a*a) */
 size_t u2pl_weight_split3_bytes(int rows, int K, int batch);
 int u2pl_weight_split3_f32(const float* w, long zw, int rows, int K, int batch, void* out, hipStream_t stream);
-/* All weight splits / all Winograd filter transforms of a model in ONE launch each (after the optimizer / EMA update; the
+/* All bf16 weight splits / all Winograd filter transforms of a model in ONE launch each (after the optimizer / EMA update; the
  * per-weight entry points above remain the lazy path).  jobs: DEVICE arrays of
  *   struct { const float* src; unsigned short* out; long seg_begin; int rows, Np, K, kind, RS, batch; }   (48 bytes)
  *     kind 0: src = [batch][rows][K]; kind 1: src = conv weight [Cout][RS][Cin] read as [rows = Cin][K = RS * Cout] (the data
@@ -355,6 +353,39 @@ int u2pl_weight_split3_f32(const float* w, long zw, int rows, int K, int batch, 
 int u2pl_weight_split3_multi_f32(const void* jobs, int njobs, long total, hipStream_t stream);
 int u2pl_weight_split3_pad_rows(int rows);
 int u2pl_wino_weight_multi_f32(const void* jobs, int njobs, long total, hipStream_t stream);
+/* The split-fp16 operands (the *_wsh_* entry points below; csrc/conv_geom.h).
+ *   u2pl_weight_split2h_f32: the matrices of u2pl_weight_split3_f32 as planes [K/32][2][Np][32] fp16 + one uint32 per matrix (bit
+ *     pattern of its max |w|) behind the planes of all of them, zero words up to a multiple of 16 bytes.  Three launches. */
+size_t u2pl_weight_split2h_bytes(int rows, int K, int batch);
+int u2pl_weight_split2h_f32(const float* w, long zw, int rows, int K, int batch, void* out, hipStream_t stream);
+/* Every split-fp16 operand of a model rebuilt from the WEIGHTS in at most four launches (clear, maxima of every kind, pieces of
+ * kinds 0 / 1, pieces of kinds 2 / 3; three where a table has no Winograd job): the bytes u2pl_weight_split2h_f32 writes for the same
+ * operand -- for kinds 2 / 3 from the U of u2pl_wino_weight_f32 --, without an fp32 U in memory and with max |w| computed once per
+ * weight.  jobs: DEVICE array of n_flat records of kinds 0 / 1 followed by n_wino records of kinds 2 / 3 (u2pl_weight_rebuild2h_job_bytes()
+ * = 72 bytes each):
+ *   struct { const float* src; unsigned short* out; long seg_begin; long amax_begin; unsigned* amax_dst;
+ *            int rows, Np, K, kind, RS, mt; int mblk_begin, pblk_begin; }
+ *     out: a u2pl_weight_split2h_bytes(rows, K, batch) buffer, batch = 1 (kinds 0 / 1) or (mt + 2)^2; Np = u2pl_weight_split3_pad_rows(rows)
+ *     kind 0: src = [rows][K]; kind 1: src = conv weight [Cout][RS][Cin] read as [rows = Cin][K = RS * Cout].  seg_begin = prefix sum of
+ *       Np * K / 8 (seg_total = the sum).  The jobs of one weight share its maximum: amax_dst = the word behind the planes of the
+ *       weight's FIRST job in the table (out + the plane bytes), amax_begin = prefix sum of rows * K / 4 over first jobs (a further job
+ *       of a weight carries the prefix reached so far: length 0; amax_total = the sum)
+ *     kind 2: src = conv weight [O][3][3][C], planes of U[z][rows = O][K = C]; kind 3: planes of U'[z][rows = C][K = O] (rotated taps);
+ *       mt = 2 or 4; C % 4 == 0.  mblk_begin / pblk_begin = prefix sums of ceil(O * C / 4 / span(1)) / ceil(Np * K / 8 / span(2)) with
+ *       span = u2pl_weight_rebuild2h_span (wino_mblocks / wino_pblocks = the sums). */
+int u2pl_weight_rebuild2h_job_bytes(void);
+int u2pl_weight_rebuild2h_span(int which);
+int u2pl_weight_rebuild2h_f32(const void* jobs, int n_flat, int n_wino, long seg_total, long amax_total, int wino_mblocks,
+                              int wino_pblocks, hipStream_t stream);
+/* "amax object" and u2pl_absmax_f32: see the split-fp16 section below */
+int u2pl_amax_words(void);
+int u2pl_absmax_f32(const float* x, long ld, long M, int C, float* out, int clear, hipStream_t stream);
+
+/* ---- igemm_ws.hip (split-fp32 implicit GEMM with pre-split weights; round 4) -------------------------------------
+ * The *_ws entry points are the conv.hip calls of the same name with a u2pl_weight_split3_f32 buffer in place of the fp32 weight
+ * pointer.  Same arithmetic, same summation order as conv.hip's split kernels: results are bit-identical to u2pl_conv2d_fwd_f32 /
+ * _bnstats / _bnact / u2pl_conv2d_dgrad_f32 / u2pl_gemm_batched_f32 under U2PL_CONV_SPLIT=1 (statistics partial sums
+ * included; stats_partial has u2pl_igemm_ws_stat_blocks rows).  Cout > 64 only (narrower layers stay on conv.hip). */
 int u2pl_igemm_ws_stat_blocks(int N, int Hout, int Wout);
 /* launch shape of the ws kernel (A/B switch, same results; env U2PL_WS_PERSIST): 1 (default) = persistent, at most one
  * block per CU working through its tiles; 0 = one block per tile */
@@ -386,34 +417,7 @@ int u2pl_gemm_batched_ws_f32(const float* x, long ldx, long zx, const void* wspl
  *     shards (bit patterns of |x|: NaN if any element is NaN).  Every x_amax / dy_amax / *_amax argument below is one.
  *   u2pl_absmax_f32: out <- max |x| over [M][C] (C % 4 == 0, ld % 4 == 0); clear != 0 zeroes the object first.  Any upper bound
  *     within ~2^8 of the true maximum keeps fp32-class accuracy; a value BELOW the maximum overflows fp16.
- *   u2pl_conv2d_fwd_bnact_wsh_f32's y_amax: NULL or an amax object for max |y| of the fused output (the next layer's x_amax).
- *   u2pl_weight_split2h_*: planes [K/32][2][Np][32] fp16 + one uint32 per matrix (bit pattern of its max |w|) behind them.
- *     job_scratch: 48 device bytes, non-NULL (kept for the ABI; the one-weight call passes its job record by value).  The multi
- *     call takes the SplitJob table of u2pl_weight_split3_multi_f32 with out = u2pl_weight_split2h_bytes buffers. */
-size_t u2pl_weight_split2h_bytes(int rows, int K, int batch);
-int u2pl_weight_split2h_f32(const float* w, long zw, int rows, int K, int batch, void* out, void* job_scratch, hipStream_t stream);
-int u2pl_weight_split2h_multi_f32(const void* jobs, int njobs, long total, hipStream_t stream);
-/* Every split-fp16 operand of a model rebuilt from the WEIGHTS in at most four launches (clear, maxima of every kind, pieces of
- * kinds 0 / 1, pieces of kinds 2 / 3; three where a table has no Winograd job): the bytes u2pl_weight_split2h_f32 writes for the same
- * operand -- for kinds 2 / 3 from the U of u2pl_wino_weight_f32 --, without an fp32 U in memory and with max |w| computed once per
- * weight.  jobs: DEVICE array of n_flat records of kinds 0 / 1 followed by n_wino records of kinds 2 / 3 (u2pl_weight_rebuild2h_job_bytes()
- * = 72 bytes each):
- *   struct { const float* src; unsigned short* out; long seg_begin; long amax_begin; unsigned* amax_dst;
- *            int rows, Np, K, kind, RS, mt; int mblk_begin, pblk_begin; }
- *     out: a u2pl_weight_split2h_bytes(rows, K, batch) buffer, batch = 1 (kinds 0 / 1) or (mt + 2)^2; Np = u2pl_weight_split3_pad_rows(rows)
- *     kind 0: src = [rows][K]; kind 1: src = conv weight [Cout][RS][Cin] read as [rows = Cin][K = RS * Cout].  seg_begin = prefix sum of
- *       Np * K / 8 (seg_total = the sum).  The jobs of one weight share its maximum: amax_dst = the word behind the planes of the
- *       weight's FIRST job in the table (out + the plane bytes), amax_begin = prefix sum of rows * K / 4 over first jobs (a further job
- *       of a weight carries the prefix reached so far: length 0; amax_total = the sum)
- *     kind 2: src = conv weight [O][3][3][C], planes of U[z][rows = O][K = C]; kind 3: planes of U'[z][rows = C][K = O] (rotated taps);
- *       mt = 2 or 4; C % 4 == 0.  mblk_begin / pblk_begin = prefix sums of ceil(O * C / 4 / span(1)) / ceil(Np * K / 8 / span(2)) with
- *       span = u2pl_weight_rebuild2h_span (wino_mblocks / wino_pblocks = the sums). */
-int u2pl_weight_rebuild2h_job_bytes(void);
-int u2pl_weight_rebuild2h_span(int which);
-int u2pl_weight_rebuild2h_f32(const void* jobs, int n_flat, int n_wino, long seg_total, long amax_total, int wino_mblocks,
-                              int wino_pblocks, hipStream_t stream);
-int u2pl_amax_words(void);
-int u2pl_absmax_f32(const float* x, long ld, long M, int C, float* out, int clear, hipStream_t stream);
+ *   u2pl_conv2d_fwd_bnact_wsh_f32's y_amax: NULL or an amax object for max |y| of the fused output (the next layer's x_amax). */
 /* producers that leave the maximum of what they write (fused: no extra pass): the entry points of the same name without
  * `_amax` plus caller-ZEROED device floats that receive max |output| (bit-pattern atomicMax: deterministic; NULL = not wanted).
  * Reference lines as for the plain forms (BatchNorm base.py:6-8 forward / backward; Winograd transforms of resnet.py:25-41). */

@@ -212,23 +212,22 @@ def test_step_equal_with_presplit_on_and_off(Kn):
 
 
 def test_one_weight_call_back_to_back(Kn):
-    """u2pl_weight_split2h_f32 passes its job record in the kernel arguments: two calls in a row (the same job_scratch, no
+    """u2pl_weight_split2h_f32 passes its job record in the kernel arguments: two calls in a row (no
     synchronisation, other host work in between) write what each call writes alone"""
     from u2pl_amd._lib import call, query
     torch.manual_seed(8)
     wa, wb = torch.randn(96, 64, device=DEV), torch.randn(3, 160, 32, device=DEV) * 3.0
     na, nb = query("u2pl_weight_split2h_bytes", 96, 64, 1), query("u2pl_weight_split2h_bytes", 160, 32, 3)
-    scratch = torch.empty(64, dtype=torch.uint8, device=DEV)
 
     def run(sync):
         a = torch.full((na,), 0xA5, dtype=torch.uint8, device=DEV)
         b = torch.full((nb,), 0xA5, dtype=torch.uint8, device=DEV)
         torch.cuda.synchronize()
-        call("u2pl_weight_split2h_f32", wa, 96 * 64, 96, 64, 1, a, scratch)
+        call("u2pl_weight_split2h_f32", wa, 96 * 64, 96, 64, 1, a)
         if sync:
             torch.cuda.synchronize()
         sorted(range(1000), key=lambda v: -v)          # (host work: whatever lay on the stack during the first call is gone)
-        call("u2pl_weight_split2h_f32", wb, 160 * 32, 160, 32, 3, b, scratch)
+        call("u2pl_weight_split2h_f32", wb, 160 * 32, 160, 32, 3, b)
         torch.cuda.synchronize()
         return a, b
 

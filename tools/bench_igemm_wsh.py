@@ -43,8 +43,7 @@ def timed(fn):
 
 def split2h(w, rows, K, batch):
     buf = torch.empty(query("u2pl_weight_split2h_bytes", rows, K, batch), dtype=torch.uint8, device=DEV)
-    scratch = torch.empty(64, dtype=torch.uint8, device=DEV)
-    call("u2pl_weight_split2h_f32", w, rows * K, rows, K, batch, buf, scratch)
+    call("u2pl_weight_split2h_f32", w, rows * K, rows, K, batch, buf)
     torch.cuda.synchronize()
     return buf
 

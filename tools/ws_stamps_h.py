@@ -15,7 +15,7 @@ for (M, K, Nn, batch) in [(10000, 512, 256, 36), (37636, 1024, 256, 1)]:
     w = torch.randn(batch * Nn * K, device=DEV) * (K ** -0.5)
     y = torch.empty(batch * M * Nn, device=DEV)
     wsh = torch.empty(query("u2pl_weight_split2h_bytes", Nn, K, batch), dtype=torch.uint8, device=DEV)
-    call("u2pl_weight_split2h_f32", w, Nn * K, Nn, K, batch, wsh, torch.empty(64, dtype=torch.uint8, device=DEV))
+    call("u2pl_weight_split2h_f32", w, Nn * K, Nn, K, batch, wsh)
     amax = torch.zeros(2048, device=DEV)
     call("u2pl_absmax_f32", x, K, batch * M, K, amax, 1)
     for _ in range(3):

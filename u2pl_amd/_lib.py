@@ -119,10 +119,15 @@ _FN = {}
 
 def call(name, *args):
     """Call entry point `name`; tensors are passed as device pointers; the HIP
-    stream (torch's current stream) is appended automatically."""
-    fn = _FN.get(name)
-    if fn is None:
-        fn = _FN[name] = getattr(lib().cdll, name)
+    stream (torch's current stream) is appended automatically.  The number of arguments is held to the header's declaration."""
+    ent = _FN.get(name)
+    if ent is None:
+        f = getattr(lib().cdll, name)
+        ent = _FN[name] = (f, len(f.argtypes) - 1 if f.argtypes else None)
+    fn, nargs = ent
+    if nargs is not None and len(args) != nargs:
+        # (ctypes passes surplus arguments on: one argument too many would land in the stream slot)
+        raise HipError(f"{name} takes {nargs} arguments before the stream (include/u2pl_hip.h), got {len(args)}")
     conv = [a.data_ptr() if hasattr(a, "data_ptr") and a.is_cuda else _ptr(a) for a in args]
     CALLS[0] += 1
     if PROFILE is not None:

@@ -15,8 +15,9 @@ FLAGS = [
 
 
 # per-file switches.  igemm_ws.hip: no SLP vectorisation -- it fuses the split's subtractions into v_pk_add_f32 (+ a
-# hazard nop each), which costs more beside matrix instructions than the two plain adds it replaces
-EXTRA = {"igemm_ws.hip": ["-fno-slp-vectorize"]}
+# hazard nop each), which costs more beside matrix instructions than the two plain adds it replaces.  operands.hip: its
+# kernels were tuned and measured in igemm_ws.hip's translation unit; they keep the switch they were compiled with
+EXTRA = {"igemm_ws.hip": ["-fno-slp-vectorize"], "operands.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

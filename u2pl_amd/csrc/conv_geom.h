@@ -1,4 +1,4 @@
-// Shared by the implicit-GEMM kernels (conv.hip, igemm_ws.hip): gather geometry, bf16 packing, the exact three-piece split.
+// Shared by the implicit-GEMM kernels (conv.hip, igemm_ws.hip) and the weight operand planes (operands.hip): gather geometry, bf16 packing, the exact three-piece split.
 #pragma once
 #include "common.h"
 

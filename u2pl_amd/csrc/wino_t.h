@@ -1,5 +1,5 @@
 // Winograd F(m x m, 3 x 3) transform matrices (m = 2, 4) as straight-line fp32 code, shared by the transform kernels of wino.hip
-// and the operand rebuild of igemm_ws.hip (which recomputes G g G^T from the taps: same code, same bits under -ffp-contract=off).
+// and the operand rebuild of operands.hip (which recomputes G g G^T from the taps: same code, same bits under -ffp-contract=off).
 #pragma once
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -95,7 +95,7 @@ template <> struct WinoT<2> {
 };
 // Row I of U = G g G^T of ONE filter, g(r, s) = tap(r, s): WinoT::gg on the three columns (only row I of each result is kept -- the
 // rest is dead code to the compiler), then WinoT::gg on that row: the operations of wino_weight_one (wino.hip) for that row, in
-// its order, so the operand rebuild of igemm_ws.hip, which recomputes the components from the taps a row at a time, gets the
+// its order, so the operand rebuild of operands.hip, which recomputes the components from the taps a row at a time, gets the
 // bits that kernel writes (no contraction: -ffp-contract=off).
 template <int MT, int I, class Tap>
 __device__ __forceinline__ void wino_filter_row(Tap&& tap, float (&r)[WinoT<MT>::A]) {

@@ -12,8 +12,8 @@ from .layout import as_rows
 # ---- weight operands derived once per step ------------------------------------------------------------------
 # The convolutions read each weight ~14 times per step (two student + two teacher passes, the backward) but the weights
 # change ONCE per step (optimizer / EMA update on the flat arenas): the operands the kernels want -- the three bf16 piece
-# planes of the split-fp32 arithmetic (u2pl_weight_split3_f32, consumed by the *_ws entry points of csrc/igemm_ws.hip), of
-# the weight itself (forward), of its transpose (data gradient) and of its Winograd transforms -- are built on first use
+# planes of the split-fp32 arithmetic (u2pl_weight_split3_f32 of csrc/operands.hip, consumed by the *_ws entry points of
+# csrc/igemm_ws.hip), of the weight itself (forward), of its transpose (data gradient) and of its Winograd transforms -- are built on first use
 # and kept until the weights change.  A cached operand is valid for (WEIGHT_EPOCH, tensor._version): the arena updates
 # (ParamArena.sgd_step / adam_step / ema_from / copy_from write through raw pointers) bump the epoch, every torch in-place
 # op (load_state_dict, init) bumps the version.  U2PL_CONV_WS=0 keeps every layer on conv.hip's in-loop split.
@@ -161,10 +161,7 @@ def _split_of(weight, kind, rows, K, batch, src, spec, h=None):
 
     def build(buf):
         w = src()
-        if h:
-            call("u2pl_weight_split2h_f32", w, rows * K, rows, K, batch, buf, torch.empty(64, dtype=torch.uint8, device=buf.device))
-        else:
-            call("u2pl_weight_split3_f32", w, rows * K, rows, K, batch, buf)
+        call("u2pl_weight_split2h_f32" if h else "u2pl_weight_split3_f32", w, rows * K, rows, K, batch, buf)
     kind = kind + ("h" if h else "")
     buf = _derived(weight, kind, nbytes, build)
     ent = weight.__dict__["_u2pl_derived"][kind]
@@ -211,12 +208,55 @@ def ws_wino(weight, transposed, mt, h=None):
 #     the plain / transposed operands, pieces of the Winograd ones; three without Winograd operands).  It reads the weights only:
 #     the Winograd components are recomputed from the nine taps in registers (no fp32 U in memory, no scratch arena, no
 #     transform launch) and max |w| is computed once per weight for its "fh" and "dh" operands.  Job record: _RB_JOB below
-#     mirrors csrc/igemm_ws.hip's RebuildJob.
+#     mirrors csrc/operands.hip's RebuildJob.
 #   bf16 planes (U2PL_CONV_H=0): one u2pl_wino_weight_multi_f32 launch into a scratch arena and one u2pl_weight_split3_multi_f32.
 # U2PL_PRESPLIT=0: off.
 PRESPLIT = {"on": os.environ.get("U2PL_PRESPLIT", "1") != "0", "tables": {}}
+# job records of the device tables (csrc/operands.hip: RebuildJob, SplitJob; csrc/wino.hip: WinoWeightJob)
 _RB_JOB = [("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("amax_begin", "<i8"), ("amax_dst", "<u8"), ("rows", "<i4"), ("Np", "<i4"),
            ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"), ("mt", "<i4"), ("mblk", "<i4"), ("pblk", "<i4")]
+_SPLIT_JOB = [("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("rows", "<i4"), ("Np", "<i4"), ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"),
+              ("batch", "<i4")]
+_WINO_JOB = [("w", "<u8"), ("U", "<u8"), ("begin", "<i8"), ("O", "<i4"), ("C", "<i4"), ("tr", "<i4"), ("mt", "<i4")]
+
+
+def _plane_extent(sp):
+    """-> (Np, 16-byte segments of ONE matrix) of an operand's spec"""
+    Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
+    return Np, Np * (sp["K"] // 8)
+
+
+def _upload(np, rec, dev):
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+
+
+def _split3_table(np, jobs, dev):
+    """jobs: [(weight, cache entry)] of bf16-plane operands -> the device tables and the arguments of u2pl_wino_weight_multi_f32 (the
+    Winograd-domain filters, into one scratch arena) and of u2pl_weight_split3_multi_f32 (which reads them right behind)"""
+    sj = np.zeros(len(jobs), dtype=np.dtype(_SPLIT_JOB))
+    wino = [(w, e) for w, e in jobs if e["spec"]["how"] == "wino"]
+    wj = np.zeros(max(len(wino), 1), dtype=np.dtype(_WINO_JOB))
+    u_off, acc = {}, 0
+    for w, e in wino:
+        u_off[id(e)] = acc
+        acc += e["spec"]["batch"] * e["spec"]["rows"] * e["spec"]["K"]
+    scratch = torch.empty(acc, dtype=torch.float32, device=dev) if acc else None
+    begin = 0
+    for i, (w, e) in enumerate(wino):
+        sp = e["spec"]
+        wj[i] = (w.data_ptr(), scratch.data_ptr() + 4 * u_off[id(e)], begin, sp["O"], sp["C"], sp["transposed"], sp["mt"])
+        begin += sp["O"] * sp["C"]
+    seg = 0
+    for i, (w, e) in enumerate(jobs):
+        sp = e["spec"]
+        Np, segs = _plane_extent(sp)
+        src = scratch.data_ptr() + 4 * u_off[id(e)] if sp["how"] == "wino" else w.data_ptr()
+        sj[i] = (src, e["buf"].data_ptr(), seg, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0, sp.get("RS", 1), sp["batch"])
+        seg += sp["batch"] * segs
+    tab = dict(seg=seg, n_wino=len(wino), wino_total=begin, sj=_upload(np, sj, dev), wj=_upload(np, wj, dev))
+    if scratch is not None:
+        tab["scratch"] = scratch
+    return tab
 
 
 def _rebuild2h_table(np, jobs, dev):
@@ -230,8 +270,8 @@ def _rebuild2h_table(np, jobs, dev):
     first = {}                          # weight -> the word that receives its maximum (behind the planes of its first job)
     for i, (w, e) in enumerate(flat):
         sp = e["spec"]
-        Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
-        if sp["batch"] != 1 or Np * (sp["K"] // 8) >= 2 ** 31:
+        Np, segs = _plane_extent(sp)
+        if sp["batch"] != 1 or segs >= 2 ** 31:
             raise HipError("presplit: unsupported plain / transposed operand %r" % (sp,))
         tail = e["buf"].data_ptr() + (sp["K"] // 32) * 2 * Np * 64
         # (a weight's further operands -- "dh" behind "fh" -- read their scale from the FIRST operand's tail word, which only this
@@ -239,20 +279,20 @@ def _rebuild2h_table(np, jobs, dev):
         dst = first.setdefault(w.data_ptr(), tail)
         rj[i] = (w.data_ptr(), e["buf"].data_ptr(), seg, amax, dst, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0,
                  sp.get("RS", 1), 0, 0, 0)
-        seg += Np * (sp["K"] // 8)
+        seg += segs
         if dst == tail:
             amax += sp["rows"] * sp["K"] // 4
     mblk = pblk = 0
     for i, (w, e) in enumerate(wino):
         sp = e["spec"]
-        Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
+        Np, segs = _plane_extent(sp)
         if sp["C"] % 4 or sp["K"] % 32 or sp["batch"] != (sp["mt"] + 2) ** 2 or sp["O"] * sp["C"] >= 2 ** 31:
             raise HipError("presplit: unsupported Winograd operand %r" % (sp,))
         rj[len(flat) + i] = (w.data_ptr(), e["buf"].data_ptr(), 0, 0, 0, sp["rows"], Np, sp["K"], 3 if sp["transposed"] else 2, 9,
                              sp["mt"], mblk, pblk)
         mblk += -(-(sp["O"] * sp["C"] // 4) // mspan)
-        pblk += -(-(Np * (sp["K"] // 8)) // pspan)
-    return dict(rj=torch.from_numpy(rj.view(np.uint8).copy()).to(dev), n_flat=len(flat), n_rwino=len(wino), seg_h=seg, amax_h=amax,
+        pblk += -(-segs // pspan)
+    return dict(rj=_upload(np, rj, dev), n_flat=len(flat), n_rwino=len(wino), seg_h=seg, amax_h=amax,
                 mblk=mblk, pblk=pblk)
 
 
@@ -283,36 +323,7 @@ def presplit(params, owner=None):
         dev = todo[0][0].device
         tab = PRESPLIT["tables"][id(owner)] = dict(key=key, n_plain=n_plain, n_h=len(todo) - n_plain, n_wino=0)
         if n_plain:
-            plain = todo[:n_plain]
-            sj = np.zeros(n_plain, dtype=np.dtype([("src", "<u8"), ("out", "<u8"), ("seg", "<i8"), ("rows", "<i4"), ("Np", "<i4"),
-                                                   ("K", "<i4"), ("kind", "<i4"), ("RS", "<i4"), ("batch", "<i4")]))
-            wino = [(w, e) for w, e, _ in plain if e["spec"]["how"] == "wino"]
-            wj = np.zeros(max(len(wino), 1), dtype=np.dtype([("w", "<u8"), ("U", "<u8"), ("begin", "<i8"), ("O", "<i4"), ("C", "<i4"),
-                                                             ("tr", "<i4"), ("mt", "<i4")]))
-            # one scratch arena for the Winograd-domain filters (read by the split launch right behind the transform launch)
-            u_off, acc = {}, 0
-            for w, e in wino:
-                sp = e["spec"]
-                u_off[id(e)] = acc
-                acc += sp["batch"] * sp["rows"] * sp["K"]
-            scratch = torch.empty(acc, dtype=torch.float32, device=dev) if acc else None
-            begin = 0
-            for i, (w, e) in enumerate(wino):
-                sp = e["spec"]
-                wj[i] = (w.data_ptr(), scratch.data_ptr() + 4 * u_off[id(e)], begin, sp["O"], sp["C"], sp["transposed"], sp["mt"])
-                begin += sp["O"] * sp["C"]
-            seg = 0
-            for i, (w, e, _) in enumerate(plain):
-                sp = e["spec"]
-                Np = query("u2pl_weight_split3_pad_rows", sp["rows"])
-                src = scratch.data_ptr() + 4 * u_off[id(e)] if sp["how"] == "wino" else w.data_ptr()
-                sj[i] = (src, e["buf"].data_ptr(), seg, sp["rows"], Np, sp["K"], 1 if sp["how"] == "transposed" else 0,
-                         sp.get("RS", 1), sp["batch"])
-                seg += sp["batch"] * Np * (sp["K"] // 8)
-            tab.update(seg=seg, n_wino=len(wino), wino_total=begin, sj=torch.from_numpy(sj.view(np.uint8).copy()).to(dev),
-                       wj=torch.from_numpy(wj.view(np.uint8).copy()).to(dev))
-            if scratch is not None:
-                tab["scratch"] = scratch
+            tab.update(_split3_table(np, [(w, e) for w, e, _ in todo[:n_plain]], dev))
         if tab["n_h"]:
             tab.update(_rebuild2h_table(np, [(w, e) for w, e, _ in todo[n_plain:]], dev))
     if tab["n_wino"]:
