@@ -330,6 +330,30 @@ int u2pl_gconv2d_wgrad_f32(const float* dy, long lddy, const float* x, long ldx,
                            int accumulate, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
                            int S, int stride, int pad, int dil, int groups, hipStream_t stream);
 
+/* ---- dwconv.hip (depthwise 3x3 convolution in exact fp32: memory-bound stencils, no MFMA) ------------------------------
+ * nn.Conv2d(C, C, 3, groups=C): the spatial half of an atrous separable convolution (the separable DeepLabv3+ decoder,
+ * decoder.kwargs.separable; light plug-in encoders).  The reference project has no such layer: there is no reference line to
+ * cite.  Argument lists are those of the gconv entry points above, and so is the layout: rows [N*H*W][ld], ld >= C (channel
+ * slices of wider buffers work); w is the module's weight (C, 1, 3, 3) = [C][9], read by all three kernels (no derived operand).
+ * Constraints (U2PL_EINVAL before any launch otherwise): groups == Cin == Cout (depth multiplier 1); C % 4 == 0; R == S == 3;
+ * stride 1 or 2; pad >= 0 and dil >= 1, both up to 2^20 (a dilation larger than the image is fine: only the taps that land
+ * inside contribute); Hout / Wout the convolution's output size; pointers (bias excepted) 16-byte aligned and ld % 4 == 0.
+ * fp32 products, fp32 accumulation in tap order, no atomics: the weight gradient sums its pixel slabs in slab order, two runs
+ * give the same bits. */
+/* forward, bias optional (NULL) */
+int u2pl_dwconv2d_fwd_f32(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, int N, int Hin,
+                          int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                          int groups, hipStream_t stream);
+/* data gradient of that layer (gather form; stride 2 by a parity test on the tap coordinates) */
+int u2pl_dwconv2d_dgrad_f32(const float* dy, long lddy, const float* w, float* dx, long lddx, int N, int Hin, int Win,
+                            int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil, int groups,
+                            hipStream_t stream);
+/* weight gradient of that layer: workspace = per-slab partial sums (0: unsupported shape); accumulate: dw += instead of dw = */
+size_t u2pl_dwconv2d_wgrad_workspace_bytes(int N, int Hout, int Wout, int Cin, int Cout, int R, int S, int groups);
+int u2pl_dwconv2d_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, float* dw, void* workspace,
+                            int accumulate, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
+                            int S, int stride, int pad, int dil, int groups, hipStream_t stream);
+
 /* ---- operands.hip (the GEMM operands derived from the weights: piece planes, their maxima, activation maxima) ----------
  * The weights of the network change once per optimizer step (train_semi.py:526-528 optimizer.step(), :531-548 the EMA
  * teacher), the convolutions read them ~14 times per step (resnet.py:120-140 through the two student and two teacher

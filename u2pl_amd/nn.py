@@ -504,28 +504,54 @@ def gconv_constraint(Cin, Cout, groups, stride):
     return None
 
 
+def dwconv_constraint(Cin, Cout, groups, R, S, stride):
+    """-> None, or the constraint of csrc/dwconv.hip that a depthwise convolution of this shape breaks (the text of the HipError)"""
+    if groups != Cin:
+        return "groups (%d) must equal in_channels (%d)" % (groups, Cin)
+    if Cout != Cin:
+        return ("out_channels (%d) must equal in_channels (%d): depth multipliers are not supported (follow the depthwise layer "
+                "with a 1x1 convolution)" % (Cout, Cin))
+    if Cin % 4:
+        return "channels must be a multiple of 4, got %d" % Cin
+    if R != 3 or S != 3:
+        return "the kernel must be 3x3, got %dx%d" % (R, S)
+    if stride not in (1, 2):
+        return "stride must be 1 or 2, got %d" % stride
+    return None
+
+
+# the two routes of _GroupedConvFn: (stem of the four C entry points, the HipError's prefix, constraint(Cin, Cout, groups, R, S,
+# stride) -> None or text)
+GCONV_ROUTE = ("u2pl_gconv2d", "grouped convolution: ",
+               lambda Cin, Cout, groups, R, S, stride: gconv_constraint(Cin, Cout, groups, stride))
+DWCONV_ROUTE = ("u2pl_dwconv2d", "depthwise convolution: ", dwconv_constraint)
+
+
 class _GroupedConvFn(torch.autograd.Function):
-    """nn.Conv2d(groups > 1) on csrc/gconv.hip: exact fp32, all three kernels read the module's own weight tensor (no derived
+    """nn.Conv2d(groups > 1) on csrc/gconv.hip, or on csrc/dwconv.hip when groups == in_channels (`route`: the two kernel trios
+    have the same argument lists): exact fp32, all three kernels read the module's own weight tensor (no derived
     operand, so nothing for presplit() / the graph capture's "operand must be current" rule).  Same contracts as _ConvFn:
     arena gradient sinks + _mark_ready, GradJoin on the input, weight gradient on the side stream."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, dil, groups, wsink, bsink, link=None):
+    def forward(ctx, x, weight, bias, stride, pad, dil, groups, wsink, bsink, link=None, route=GCONV_ROUTE):
+        stem, what, constraint = route
         x, ldx = as_rows(x)
         N, Cin, H, W = x.shape
         Cout, cig, R, S = weight.shape
-        why = gconv_constraint(Cin, Cout, groups, stride)
+        why = constraint(Cin, Cout, groups, R, S, stride)
         if why is None and cig * groups != Cin:
             why = "weight has %d input channels per group, the input %d channels in %d groups" % (cig, Cin, groups)
         if why is not None:
-            raise HipError("grouped convolution: " + why)
+            raise HipError(what + why)
         _check_weight_layout(weight, "Cin/groups")
         Ho, Wo = _out_size(H, R, stride, pad, dil), _out_size(W, S, stride, pad, dil)
         ctx.set_materialize_grads(False)
         ctx.link = link
         y = new_act(N, Cout, Ho, Wo, x.device)
-        call("u2pl_gconv2d_fwd_f32", x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
+        call(stem + "_fwd_f32", x, ldx, weight, bias, y, Cout, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
         ctx.save_for_backward(x, weight)
+        ctx.stem = stem
         ctx.geom = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups, ldx)
         ctx.has_bias = bias is not None
         ctx.wsink, ctx.bsink = wsink, bsink
@@ -534,8 +560,9 @@ class _GroupedConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         if gy is None:
-            return (None,) * 10
+            return (None,) * 11
         x, weight = ctx.saved_tensors
+        stem = ctx.stem
         N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups, ldx = ctx.geom
         gy, ldg = as_rows(gy)
         dev = gy.device
@@ -545,16 +572,16 @@ class _GroupedConvFn(torch.autograd.Function):
             raise HipError("gradient join on a convolution whose input needs no gradient")
         if ctx.needs_input_grad[0]:
             dx = new_act(N, Cin, H, W, dev)
-            call("u2pl_gconv2d_dgrad_f32", gy, ldg, weight, dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
+            call(stem + "_dgrad_f32", gy, ldg, weight, dx, Cin, N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
             if join is not None:
                 dx = join.settle(dx, False)         # (no fused accumulate form: the running sum is added in place)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         with _wgrad_side(need_w or need_b, gy, x) as side:
             if need_w:
                 sink = ctx.wsink
-                wsb = _ws(query("u2pl_gconv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups), dev)
+                wsb = _ws(query(stem + "_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups), dev)
                 tgt = sink if sink is not None else torch.empty_like(weight)
-                call("u2pl_gconv2d_wgrad_f32", gy, ldg, x, ldx, tgt, wsb, int(sink is not None), N, H, W, Cin, Ho, Wo, Cout, R, S,
+                call(stem + "_wgrad_f32", gy, ldg, x, ldx, tgt, wsb, int(sink is not None), N, H, W, Cin, Ho, Wo, Cout, R, S,
                      stride, pad, dil, groups)
                 if sink is None:
                     dw = tgt
@@ -563,12 +590,13 @@ class _GroupedConvFn(torch.autograd.Function):
                 db = _bias_grad(gy, ldg, N * Ho * Wo, Cout, Cout, ctx.bsink)
         if side is not None and (dw is not None or db is not None):      # returned to autograd on the main stream
             torch.cuda.current_stream().wait_stream(side)
-        return dx, dw, db, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None
 
 
 class Conv2d(nn.Module):
     """nn.Conv2d with torch's default init, weight stored channels_last.  groups > 1 (the 3x3 of a ResNeXt bottleneck) runs on
-    csrc/gconv.hip (_GroupedConvFn); the shape constraints of that route are reported at the first call, not at construction."""
+    csrc/gconv.hip, groups == in_channels (depthwise: separable decoders, light encoders) on csrc/dwconv.hip (both through
+    _GroupedConvFn); the shape constraints of those routes are reported at the first call, not at construction."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, groups=1):
         super().__init__()
@@ -593,8 +621,11 @@ class Conv2d(nn.Module):
         """stat_pivot: running_mean of a following train-mode BatchNorm -> returns (y, fused BN sums).
         grad_link: a GradJoin shared with the other consumers of x (grad_join)."""
         if self.groups != 1:
+            # depthwise is decided first; a depth multiplier (out_channels = k * in_channels) goes there too and is refused by name
+            route = DWCONV_ROUTE if self.groups == self.in_channels else GCONV_ROUTE
             y = _GroupedConvFn.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups,
-                                     _grad_sink(self.weight), _grad_sink(self.bias) if self.bias is not None else None, grad_link)
+                                     _grad_sink(self.weight), _grad_sink(self.bias) if self.bias is not None else None, grad_link,
+                                     route)
             return y if stat_pivot is None else (y, None)     # statistics by the stand-alone pass (_bn_local_sums)
         out = _ConvFn.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation,
                             _grad_sink(self.weight), _grad_sink(self.bias) if self.bias is not None else None, stat_pivot,
