@@ -253,7 +253,10 @@ int u2pl_gemm_batched_f32(const float* x, long ldx, long zx, const float* w, lon
    base.py:54-83, decoder.py:60-106,132-138): V[a*a][tiles][C] <- x ; U[a*a][O][C] <- w ([O][3][3][C]);
    Mb[a*a][tiles][O] = V . U^T (u2pl_gemm_batched_f32) ; y <- Mb (+bias).  a = mt + 2, tiles = u2pl_wino_tiles.
    transposed = 1 builds U'[a*a][C][O] (taps rotated) for the data gradient.  stats_partial (rows =
-   u2pl_wino_stat_blocks) receives the pivot-shifted BatchNorm column sums of y like u2pl_conv2d_fwd_bnstats_f32. */
+   u2pl_wino_stat_blocks) receives the pivot-shifted BatchNorm column sums of y like u2pl_conv2d_fwd_bnstats_f32.
+   Every transform moves 16 bytes per access: C % 4 == 0 (O % 4 == 0), and every row pitch (ldx, ldg, ldy, ldr) is a multiple
+   of 4 floats, as for u2pl_absmax_f32 and the bnact forms -- U2PL_EINVAL before any launch otherwise.  Statistics need
+   4 <= O <= 1024; u2pl_wino_stat_blocks returns 0 for O < 4. */
 size_t u2pl_wino_tiles(int N, int H, int W, int dil, int mt);
 int u2pl_wino_stat_blocks(long tiles, int O);
 int u2pl_wino_input_f32(const float* x, long ldx, int N, int H, int W, int C, int dil, int mt, float* V,

@@ -69,6 +69,28 @@ def test_winograd_layer_policy():
         K.CONV_ALGO.update(saved)
 
 
+def test_winograd_statistics_rows_and_refusals_need_no_gpu():
+    """u2pl_wino_stat_blocks: rows of the statistics partials, 256 / (O/4) tiles per block; 0 for O < 4 (it used to divide by
+    O / 4 = 0 there).  The Winograd entry points refuse a shape before any launch -- so also without a device: statistics on
+    O < 4 or O > 1024, and a row pitch that is not a multiple of 4 floats (16-byte accesses), like u2pl_absmax_f32."""
+    L = _lib.lib()
+    assert L.u2pl_wino_stat_blocks(27, 256) == 7 and L.u2pl_wino_stat_blocks(28, 256) == 7
+    assert L.u2pl_wino_stat_blocks(32, 304) == 11           # 76 float4 columns: 3 tiles per block
+    assert L.u2pl_wino_stat_blocks(4, 1024) == 4 and L.u2pl_wino_stat_blocks(512, 4) == 2
+    for O in (0, 1, 2, 3):
+        assert L.u2pl_wino_stat_blocks(100, O) == 0
+    EINVAL = 1001
+    for O in (2, 1028):
+        assert L.u2pl_wino_output_f32(None, 1, 4, 4, O, 1, 4, None, None, 1028, 1, None, None) == EINVAL      # (stats != NULL)
+    for name in ("u2pl_wino_input_f32", "u2pl_wino_gy_f32"):
+        for ld in (9, 10, 11):
+            assert getattr(L, name)(None, ld, 1, 4, 4, 8, 1, 4, None, None) == EINVAL
+    for name in ("u2pl_wino_input_amax_f32", "u2pl_wino_gy_amax_f32"):
+        assert getattr(L, name)(None, 10, 1, 4, 4, 8, 1, 2, None, None, None) == EINVAL
+    assert L.u2pl_wino_output_f32(None, 1, 4, 4, 8, 1, 4, None, None, 10, None, None, None) == EINVAL
+    assert L.u2pl_absmax_f32(None, 10, 4, 8, None, 0, None) == EINVAL
+
+
 def test_conv_arithmetic_switch_and_statistics_block_count():
     """u2pl_conv_set_split / u2pl_conv_get_split (host state, no GPU needed) and the planner query that sizes the fused
     BatchNorm-statistics partials: in the split form every launch is ONE grid of 128-row body tiles (no tail launch), with

@@ -2,7 +2,7 @@
 tests/plane_ref.py, a pure-torch statement of the format: every byte of the buffer (pieces, swizzle, zero padding rows, maxima words,
 the zero tail) with torch.equal.  The operands are built through the C entry points of the lazy path: on the weight as it lies, on
 the output of u2pl_weight_transpose_f32 and on the output of u2pl_wino_weight_f32 (the fp32 U from the GPU is the reference's input:
-the transform itself is held by tests/test_gpu_igemm_ws.py).  The batched rebuild is held to the lazy path's bytes by
+the transform itself is held to float64 by tests/test_gpu_wino_stages.py).  The batched rebuild is held to the lazy path's bytes by
 tests/test_gpu_presplit_taps.py, non-finite weights by its test_maxima_edge_cases."""
 import os
 import sys

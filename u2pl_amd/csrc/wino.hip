@@ -381,8 +381,9 @@ U2PL_API size_t u2pl_wino_tiles(int N, int H, int W, int dil, int mt) {
     if (wino_geom(N, H, W, 4, dil, mt, g)) return 0;
     return (size_t)g.tiles;
 }
-// rows of the [nblk][2][O] statistics partials written by u2pl_wino_output_f32
+// rows of the [nblk][2][O] statistics partials written by u2pl_wino_output_f32 (0: no statistics for this O, see run_wino_output)
 U2PL_API int u2pl_wino_stat_blocks(long tiles, int O) {
+    if (O < 4 || tiles < 0) return 0;
     const int tpb = 256 / (O / 4) > 0 ? 256 / (O / 4) : 1;
     return (int)((tiles + tpb - 1) / tpb);
 }
@@ -391,7 +392,7 @@ U2PL_API int u2pl_wino_stat_blocks(long tiles, int O) {
 static int run_wino_input(const float* x, long ldx, int N, int H, int W, int C, int dil, int mt, float* V, float* v_amax,
                           hipStream_t stream) {
     WinoGeom g;
-    if (wino_geom(N, H, W, C, dil, mt, g)) return U2PL_EINVAL;
+    if (wino_geom(N, H, W, C, dil, mt, g) || (ldx & 3)) return U2PL_EINVAL;      // (16-byte loads: the pitch keeps them aligned)
     const long xb = (((long)N * H * W - 1) * ldx + C) * 4;
     if (xb >= (1L << 31)) return U2PL_EINVAL;
     const long total = g.tiles * (C / 4);
@@ -429,8 +430,8 @@ U2PL_API int u2pl_wino_weight_f32(const float* w, int O, int C, int transposed, 
 static int run_wino_output(const float* Mb, int N, int H, int W, int O, int dil, int mt, const float* bias, float* y,
                            long ldy, float* stats_partial, const float* pivot, const BnEpi& epi, hipStream_t stream) {
     WinoGeom g;
-    if (wino_geom(N, H, W, O, dil, mt, g)) return U2PL_EINVAL;
-    if (stats_partial && (O / 4 > 256 || (O & 3))) return U2PL_EINVAL;
+    if (wino_geom(N, H, W, O, dil, mt, g) || (ldy & 3)) return U2PL_EINVAL;
+    if (stats_partial && (O < 4 || O / 4 > 256 || (O & 3))) return U2PL_EINVAL;
     const long total = g.tiles * (O / 4);
     const unsigned nblk = stats_partial ? (unsigned)u2pl_wino_stat_blocks(g.tiles, O) : (unsigned)cdiv(total, 256);
     if (mt == 4) U2PL_LAUNCH(k_wino_output<4>, dim3(nblk), dim3(256), 0, stream, Mb, g, O, bias, y, ldy, stats_partial, pivot, epi);
@@ -465,7 +466,7 @@ U2PL_API int u2pl_wino_output_bnact_amax_f32(const float* Mb, int N, int H, int 
 static int run_wino_gy(const float* gy, long ldg, int N, int H, int W, int O, int dil, int mt, float* Mg, float* mg_amax,
                        hipStream_t stream) {
     WinoGeom g;
-    if (wino_geom(N, H, W, O, dil, mt, g)) return U2PL_EINVAL;
+    if (wino_geom(N, H, W, O, dil, mt, g) || (ldg & 3)) return U2PL_EINVAL;
     const long gb = (((long)N * H * W - 1) * ldg + O) * 4;
     if (gb >= (1L << 31)) return U2PL_EINVAL;
     const long total = g.tiles * (O / 4);
