@@ -463,6 +463,8 @@ static int run_igemm(const float* x, long ldx, const float* w, const float* bias
         int rc = launch_igemm<1, 2, 4, 1>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy);
         if (rc || p.nblk_tail == 0) return rc;
         float* st = stats ? stats + (long)p.nblk_body * 2 * g.Cout : nullptr;
+        // (the plan counts a tail_tm == 4 tail in 128-row blocks: the launch must have that BM, or the statistics overrun the plan)
+        if (p.tail_tm == 4) return launch_igemm<1, 1, 4, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
         if (p.tail_tm == 2) return launch_igemm<2, 2, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
         if (p.tail_tn == 2) return launch_igemm<1, 2, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
         return launch_igemm<1, 1, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
