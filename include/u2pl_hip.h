@@ -417,6 +417,15 @@ int u2pl_igemm_ws_stat_blocks(int N, int Hout, int Wout);
 /* launch shape of the ws kernel (A/B switch, same results; env U2PL_WS_PERSIST): 1 (default) = persistent, at most one
  * block per CU working through its tiles; 0 = one block per tile */
 int u2pl_igemm_ws_set_persist(int on);
+/* the tile plan a *_ws_* / *_wsh_* call of M output rows, reduction length K = R * S * Cin, Cout columns and `batch` matrices runs under
+ * (host query, no launch; what u2pl_conv2d_fwd_stat_blocks is to conv.hip's planner).  np: pieces per operand, 3 = the *_ws_* calls,
+ * 2 = *_wsh_*.  out[3] = {kind, wide tiles, narrow tiles}: kind 0 = 128 x 256 tiles only, 1 = 128 x 128 tiles only, 2 = mixed in one
+ * launch (the full rounds as `wide` 128 x 256 tiles, the remainder as `narrow` 128 x 128 tiles), 3 = the same as two launches
+ * (U2PL_WS_MIX2=1).  Follows U2PL_WS_NARROW, U2PL_WS_MIX2, U2PL_WS_FIX2 and u2pl_igemm_ws_set_persist like the launches do.
+ * The query answers for the model alone and does not tell whether a call can be launched: K is used as K / 32 chunks (the launches
+ * refuse Cin % 32 != 0), Cout <= 64 gets the narrow plan although the callers keep such layers on conv.hip, and pointers, pitches and
+ * extents are not seen.  Refused (U2PL_EINVAL): a non-positive size, np other than 2 or 3, out == NULL, M >= 2^31 or 2^30 tiles. */
+int u2pl_igemm_ws_plan(long M, int K, int Cout, int batch, int np, int* out);
 int u2pl_conv2d_fwd_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y, long ldy, int N,
                            int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad,
                            int dil, hipStream_t stream);

@@ -1,7 +1,8 @@
 """The direct implicit-GEMM kernel k_conv_igemm<TM, TN, WM, BF> (u2pl_amd/csrc/conv.hip) on its own: the planner and kernel choice
 restated, a float64 reference and per-element bound for every entry point, a numpy fp32 emulation of the kernel's order with
 switchable faults, and the table of tile / loop / gather / pitch edges -- shared by tests/test_igemm_cpu.py and
-tests/test_gpu_igemm_bounds.py.  Not a conftest: imported by name.
+tests/test_gpu_igemm_bounds.py.  Not a conftest: imported by name.  Also the tile plan of the pre-split GEMMs (csrc/igemm_ws.hip
+plan_igemm_ws) restated, for tests/test_ws_plan_cpu.py.
 
     Y[m][co] = sum over (r, s, ci) of X[gather(m, r, s)][ci] * W[co][r][s][ci]        K = R S Cin
 
@@ -147,6 +148,56 @@ def stat_blocks(launches):
 
 def shape_of(l):
     return "<%d, %d, %d, %d>" % (l.TM, l.TN, l.WM, l.BF)
+
+
+# ---- plan_igemm_ws (csrc/igemm_ws.hip): the tile plan of the pre-split GEMMs ----------------------------------------------------------
+WS_WIDE, WS_NARROW, WS_MIXED, WS_MIXED2 = 0, 1, 2, 3
+WsPlan = collections.namedtuple("WsPlan", "kind wide narrow")
+
+
+def plan_igemm_ws(M, K, Cout, batch, np_, narrow=None, mix2=0, fix2=2.0, persist=1):
+    """u2pl_igemm_ws_plan.  np_: pieces per operand (3 six bf16 products, 2 split-fp16); narrow: the integer value of U2PL_WS_NARROW (None:
+    unset), mix2: U2PL_WS_MIX2, fix2: U2PL_WS_FIX2, persist: u2pl_igemm_ws_set_persist.  Costs in units of one 32-deep chunk of a 128 x 256
+    tile: a narrow tile takes 0.5 x 1.15 of it, a tile has a fixed cost of 4 (wide) or 2 (narrow) units, `fix2` times that for split-fp16;
+    the mixed plan pays 2 more (8 as two launches) and must beat the wide plan by 3 %."""
+    mt, nkc = cdiv(M, 128), K // BK
+    ntw, ntn = cdiv(Cout, 256), cdiv(Cout, 128)
+    tw, tn = mt * ntw * batch, mt * ntn * batch
+    wide, nar = WsPlan(WS_WIDE, tw, 0), WsPlan(WS_NARROW, 0, tn)
+    if Cout <= 128:
+        return nar
+    fix = 1.0 if np_ == 3 else fix2
+    cw1, cn1 = nkc + 4.0 * fix, 0.5 * 1.15 * nkc + 2.0 * fix
+    cw, cn = float(cdiv(tw, NUM_CUS)) * cw1, float(cdiv(tn, NUM_CUS)) * cn1
+    if narrow == 0:
+        return wide
+    if narrow == 1:
+        return nar if Cout <= 256 else wide
+    full = tw // NUM_CUS * NUM_CUS
+    rem = tw - full
+    can_mix = narrow != 2 and persist and ntn == 2 * ntw and full > 0 and rem > 0 and 2 * rem <= NUM_CUS
+    cm = float(full // NUM_CUS) * cw1 + cn1 + (8.0 if mix2 else 2.0) * fix if can_mix else 1e30
+    if cm < 0.97 * cw and cm < cn:
+        return WsPlan(WS_MIXED2 if mix2 else WS_MIXED, full, 2 * rem)
+    return nar if cn < 0.97 * cw else wide
+
+
+def ws_plan_sweep():
+    """(M, K, Cout, batch) across every boundary of the model: Cout 128 / 129 (the narrow-only range), 256 / 257 (one or two wide column
+    tiles; 257 .. 384 has three narrow ones: no mixing), 512; wide tile counts either side of a round (256) and of the largest mixable
+    remainder (2 rem = 256 | 258); K from one chunk to 4608, with the chunk counts between which the mixed plan starts to win on 257 tiles:
+    13 / 14 (np 3) and 26 / 27 (np 2) in one launch, 53 / 54 and 106 / 107 as two launches (U2PL_WS_MIX2)"""
+    out = []
+    for Cout in (65, 128, 129, 256, 257, 384, 385, 512, 513, 1024, 2048):
+        ntw = cdiv(Cout, 256)
+        for batch in (1, 16, 36):
+            mts = set()
+            for tw in (1, 128, 255, 256, 257, 300, 383, 384, 385, 511, 512, 513, 640, 641, 792, 1000):
+                mts |= {max(1, tw // (ntw * batch)), cdiv(tw, ntw * batch)}
+            for mt in sorted(mts):
+                for K in (32, 256, 416, 448, 512, 832, 864, 1024, 1696, 1728, 2304, 3392, 3424, 4608):
+                    out.append((mt * 128 - 5, K, Cout, batch))
+    return out
 
 
 # ---- geometry -------------------------------------------------------------------------------------------------------------------------

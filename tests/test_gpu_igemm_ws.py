@@ -69,6 +69,19 @@ CASES = [
 ]
 
 
+# the two cases of the table that are there for the mixed plan -> (kind, wide tiles, narrow tiles) of u2pl_igemm_ws_plan, forward
+MIXED_CASES = {(512, 256, 1): (2, 256, 102), (64, 512, 3): (2, 256, 128)}
+WS_PLAN_SWITCHES = ("U2PL_WS_NARROW", "U2PL_WS_MIX2", "U2PL_WS_FIX2", "U2PL_WS_PERSIST")
+
+
+def _ws_plan(M, Kred, Cout, batch, np_):
+    import ctypes
+    from u2pl_amd._lib import lib
+    out = (ctypes.c_int * 3)()
+    assert lib().u2pl_igemm_ws_plan(M, Kred, Cout, batch, np_, out) == 0
+    return tuple(out)
+
+
 def _run(Kn, ws_on, conv, x, gy, pivot=None):
     Kn.CONV_WS["on"] = ws_on
     x = x.detach().clone().requires_grad_(True)
@@ -95,6 +108,8 @@ def test_ws_forward_dgrad_stats_bit_identical(Cin, Cout, k, stride, dil, H, W, N
     Wo = (W + 2 * dil * (k // 2) - dil * (k - 1) - 1) // stride + 1
     gy = torch.randn(N, Cout, Ho, Wo, device=DEV).contiguous(memory_format=CL)
     pivot = torch.randn(Cout, device=DEV) * 0.1
+    if (Cin, Cout, k) in MIXED_CASES and not any(os.environ.get(v) for v in WS_PLAN_SWITCHES):
+        assert _ws_plan(N * Ho * Wo, k * k * Cin, Cout, 1, 3) == MIXED_CASES[(Cin, Cout, k)]       # (what the table calls the mixed plan is)
     _check_case(Kn, conv, x, gy, pivot, Cout)
 
 
@@ -482,6 +497,73 @@ def test_wsh_same_bits_across_tile_plans(Cin, Cout, k, stride, dil, H, W, N, bia
     assert torch.equal(outs[0][3][: 2 * Cout], outs[1][3][: 2 * Cout])          # (slot 2C, the row count, is the BatchNorm's to fill)
 
 
+# The smallest pointwise forward that runs under all four plans: 257 wide tiles (one round + 1; mixing needs a full round), Cout = 256, and
+# the first reduction length at which the model still mixes when the plan costs two launches (U2PL_WS_MIX2 = 1: 8 fixed units instead of
+# 2; 1.575 n + 14 < 1.725 n + 6 chunks for the six-product planes, 1.575 n + 28 < 1.725 n + 12 for split-fp16 with U2PL_WS_FIX2 = 2:
+# n = 54 and 107 chunks of 32).  In one launch the mixed plan wins from 14 and 27 chunks on (tests/test_ws_plan_cpu.py).  (np, Cin):
+PLAN_BITS = ((3, 1728), (2, 3424))
+PLAN_ROWS, PLAN_COUT = 257 * 128, 256
+
+
+def _plan_bits_outputs():
+    """the pointwise forward with fused statistics of PLAN_BITS under this process's switches -> [(plan, y, 2 Cout sums)] (CPU tensors)"""
+    Kn = K()
+    Kn.CONV_ALGO.update(wino=0)
+    Kn.CONV_WS["on"] = True
+    out = []
+    for np_, Cin in PLAN_BITS:
+        Kn.CONV_H["on"] = np_ == 2
+        # the call must reach k_igemm_ws, or the plans compared are no plans: the pre-split route on, no bf16-operand student
+        assert Kn._ws_ok(PLAN_COUT, Cin) and not Kn.CONV_ALGO.get("bf16", 0), (dict(Kn.CONV_ALGO), dict(Kn.CONV_WS))
+        g = torch.Generator().manual_seed(100 + Cin)
+        conv = Kn.Conv2d(Cin, PLAN_COUT, 1, bias=True)
+        with torch.no_grad():
+            conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) / Cin ** 0.5)
+            conv.bias.copy_(torch.randn(PLAN_COUT, generator=g))
+        conv = conv.to(DEV)
+        gd = torch.Generator(device=DEV).manual_seed(200 + Cin)       # (the same seeded device generator in every process: the same x)
+        x = torch.randn(1, 257, 128, Cin, device=DEV, generator=gd).permute(0, 3, 1, 2)
+        pivot = (torch.randn(PLAN_COUT, generator=g) * 0.1).to(DEV)
+        y, sums = conv(x, stat_pivot=pivot)
+        sums = Kn.finished_sums(sums, PLAN_COUT)
+        torch.cuda.synchronize()
+        out.append((_ws_plan(PLAN_ROWS, Cin, PLAN_COUT, 1, np_), y.detach().cpu(), sums.detach()[: 2 * PLAN_COUT].cpu()))
+    return out
+
+
+@pytest.fixture(scope="module")
+def plan_bits_default():
+    """the outputs under this process's own (default) plan, computed once for the forced plans to be compared with"""
+    assert not any(os.environ.get(v) for v in WS_PLAN_SWITCHES), "run the suite without the tile-plan switches: this test sets each itself"
+    saved = (dict(K().CONV_ALGO), dict(K().CONV_WS), dict(K().CONV_H))
+    try:
+        return _plan_bits_outputs()
+    finally:
+        for d, s_ in zip((K().CONV_ALGO, K().CONV_WS, K().CONV_H), saved):
+            d.update(s_)
+
+
+@pytest.mark.parametrize("name,value,plan", [("U2PL_WS_NARROW", "0", (0, 257, 0)), ("U2PL_WS_NARROW", "1", (1, 0, 514)), ("U2PL_WS_MIX2", "1", (3, 256, 2))])
+def test_same_bits_under_the_wide_narrow_mixed_and_two_launch_plans(name, value, plan, plan_bits_default, tmp_path):
+    """INTEGRATION.md promises "Same bits" for U2PL_WS_NARROW and U2PL_WS_MIX2: a tile plan changes which block computes a tile, never the
+    order of a tile's products or of its statistics rows.  The switches are read once per process: the default (mixed, asserted through the
+    query) runs here, the forced plan in one child of this file, which is ended at its time limit; y and the 2 Cout statistics sums must
+    agree bit for bit."""
+    import subprocess
+    mine = plan_bits_default
+    assert [o[0] for o in mine] == [(2, 256, 2), (2, 256, 2)]                 # mixed: 256 wide tiles + the 257th as two narrow ones
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = str(tmp_path / "forced.pt")
+    env = dict(os.environ, PYTHONPATH=root)
+    env[name] = value
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), path], cwd=root, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (name, value, r.stderr[-2000:])
+    for (np_, Cin), a, b in zip(PLAN_BITS, mine, torch.load(path)):
+        assert tuple(b[0]) == plan, (name, value, np_, b[0])
+        assert torch.equal(a[1], b[1]), (name, value, np_, "y differs", float((a[1] - b[1]).abs().max()))
+        assert torch.equal(a[2], b[2]), (name, value, np_, "statistics differ")
+
+
 @pytest.mark.parametrize("Cin,Cout,dil,H,W,N", [(256, 256, 2, 33, 29, 2), (512, 512, 4, 21, 21, 1), (128, 128, 1, 37, 37, 1)])
 def test_wsh_winograd_layers_against_float64(Cin, Cout, dil, H, W, N, wsh_switch):
     from u2pl_amd._lib import query
@@ -706,3 +788,8 @@ def test_wsh_power_of_two_homogeneity_is_exact_at_the_headline_sizes(Cin, Cout, 
     assert torch.equal(dw1, dw0 * 2.0 ** (a + b))
     assert torch.equal(s1[:Cout], s0[:Cout] * 2.0 ** (a + c))
     assert torch.equal(s1[Cout:2 * Cout], s0[Cout:2 * Cout] * 4.0 ** (a + c))
+
+
+if __name__ == "__main__":          # a child of test_same_bits_under_the_wide_narrow_mixed_and_two_launch_plans: argv[1] = where to save
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    torch.save(_plan_bits_outputs(), sys.argv[1])

@@ -348,14 +348,23 @@ __global__ __launch_bounds__(128 * WM, WM) void k_conv_igemm(const float* __rest
     }
 }
 
-template <int TM, int TN, int WM = 2, int BF = 0>
-static int launch_igemm(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy,
-                        const ConvGeom& g, long m_begin, long m_end, hipStream_t stream, float* stats = nullptr,
-                        const float* pivot = nullptr, int batch = 1, long zx = 0, long zw = 0, long zy = 0,
-                        const BnEpi* epi = nullptr) {
+// one call of the implicit GEMM, filled once by the entry point: operands and pitches, geometry, stream, fused statistics, batch strides
+// (batch > 1: gridDim.z independent GEMMs, element strides zx / zw / zy) and the eval-BatchNorm epilogue (epi.mean == NULL: none)
+struct IgemmCall {
+    const float* x; long ldx; const float *w, *bias; float* y; long ldy; ConvGeom g; hipStream_t stream;
+    float* stats; const float* pivot; int batch; long zx, zw, zy; BnEpi epi;
+};
+static IgemmCall igemm_call(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const ConvGeom& g,
+                            hipStream_t stream, float* stats = nullptr, const float* pivot = nullptr) {
+    return IgemmCall{x, ldx, w, bias, y, ldy, g, stream, stats, pivot, 1, 0, 0, 0, BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}};
+}
+
+// output rows [m_begin, m_end) of the call; stats: where this launch's statistics partials start
+template <int TM, int TN, int WM, int BF>
+static int launch_igemm(const IgemmCall& c, long m_begin, long m_end, float* stats) {
     constexpr int BM = 32 * TM * WM, BN = 64 * TN;
     if (m_end <= m_begin) return 0;
-    const BnEpi ep = epi ? *epi : BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const ConvGeom& g = c.g;
     const size_t lds_op = BF == 3 ? (size_t)3 * (BM + BN) * LDPH * sizeof(unsigned short) : (size_t)2 * (BM + BN) * LDP * sizeof(float);
     const size_t lds_epi = (size_t)(4 * WM / 2) * (32 * TM) * (32 * TN + 4) * sizeof(float);     // the epilogue's per-wave transpose regions
     const size_t lds = lds_op > lds_epi ? lds_op : lds_epi;
@@ -365,20 +374,13 @@ static int launch_igemm(const float* x, long ldx, const float* w, const float* b
         attr_set = true;
     }
     // byte extents of the gathered tensor and of the weight matrix (raw-buffer descriptors)
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    const long wb = (long)g.Cout * g.R * g.S * g.Cin * 4;
-    if (xb >= (1L << 31) || wb >= (1L << 31)) return U2PL_EINVAL;
-    dim3 grid((unsigned)cdiv(m_end - m_begin, BM), (unsigned)cdiv(g.Cout, BN), (unsigned)batch);
-    U2PL_LAUNCH((k_conv_igemm<TM, TN, WM, BF>), grid, dim3(128 * WM), lds, stream, x, ldx, w, bias, y, ldy, g, (unsigned)xb,
-                       (unsigned)wb, m_begin, m_end, stats, pivot, zx, zw, zy, ep);
+    unsigned xb, wb;
+    if (!span_bytes(geom_rows_in(g), c.ldx, g.Cin, xb) || !span_bytes(1, 0, (long)g.Cout * g.R * g.S * g.Cin, wb)) return U2PL_EINVAL;
+    dim3 grid((unsigned)cdiv(m_end - m_begin, BM), (unsigned)cdiv(g.Cout, BN), (unsigned)c.batch);
+    U2PL_LAUNCH((k_conv_igemm<TM, TN, WM, BF>), grid, dim3(128 * WM), lds, c.stream, c.x, c.ldx, c.w, c.bias, c.y, c.ldy, g, xb, wb, m_begin,
+                m_end, stats, c.pivot, c.zx, c.zw, c.zy, c.epi);
     U2PL_LAUNCH_CHECK();
     return 0;
-}
-
-static int log2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
 }
 
 // the fp32 products' arithmetic: 1 (default) = split fp32 on the bf16 matrix cores (k_conv_igemm BF == 3), 0 = the fp32
@@ -403,7 +405,7 @@ static double tail_cost(long rows, int cout, int bm, int bn, double eff) {
 // the planner's decisions, shared by the launcher and by the stat-block query
 struct IgemmPlan { long m_body; int tail_tm, tail_tn; int nblk_body, nblk_tail; };
 static IgemmPlan plan_igemm(const ConvGeom& g, int batch = 1) {
-    const long M = (long)g.N * g.Hout * g.Wout;
+    const long M = geom_rows_out(g);
     IgemmPlan p = {M, 0, 0, 0, 0};
     if (g.Cout <= 64) { p.nblk_body = cdiv(M, 128); return p; }   // single <2,1> launch
     const int nt = cdiv(g.Cout, 128) * batch;
@@ -437,52 +439,49 @@ static IgemmPlan plan_igemm(const ConvGeom& g, int batch = 1) {
     p.nblk_tail = p.tail_tm == 4 ? cdiv(tail, 128) : cdiv(tail, 64 * p.tail_tm);
     return p;
 }
-static int run_igemm(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy,
-                     const ConvGeom& g, hipStream_t stream, float* stats = nullptr, const float* pivot = nullptr,
-                     int batch = 1, long zx = 0, long zw = 0, long zy = 0, int bf = 0, const BnEpi* epi = nullptr) {
-    if (g.Cin % BK) return U2PL_EINVAL;
-    if (epi && (bf == 1 || stats || batch != 1 || (g.Cout & 3))) return U2PL_EINVAL;
-    const long M = (long)g.N * g.Hout * g.Wout;
-    const IgemmPlan p = plan_igemm(g, batch);
-    if (bf == 0 && conv_split()) bf = 3;
-    if (bf == 3) {   // split-fp32 variants of the same tile shapes (all epilogues)
-        if (g.Cout <= 64) return launch_igemm<2, 1, 2, 3>(x, ldx, w, bias, y, ldy, g, 0, M, stream, stats, pivot, batch, zx, zw, zy, epi);
-        static int waves3 = 0;
-        if (!waves3) { const char* e = getenv("U2PL_IGEMM_WAVES"); waves3 = (e && atoi(e) == 4) ? 4 : 8; }
-        int rc = waves3 == 8 ? launch_igemm<1, 2, 4, 3>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy, epi)
-                             : launch_igemm<2, 2, 2, 3>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy, epi);
-        if (rc || p.nblk_tail == 0) return rc;
-        float* st = stats ? stats + (long)p.nblk_body * 2 * g.Cout : nullptr;
-        if (p.tail_tm == 4) return launch_igemm<1, 1, 4, 3>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-        if (p.tail_tm == 2) return launch_igemm<2, 2, 2, 3>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-        if (p.tail_tn == 2) return launch_igemm<1, 2, 2, 3>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-        return launch_igemm<1, 1, 2, 3>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
+// the six tile shapes <TM, TN, WM> of k_conv_igemm: 128 x 64 on 4 waves (Cout <= 64), the 128 x 128 body on 8 or on 4 waves, and the
+// tails 128 x 64 on 8 waves, 64 x 128 and 64 x 64
+enum IgemmTile { T_212, T_124, T_222, T_114, T_122, T_112 };
+template <int BF>
+static int launch_igemm_tile(IgemmTile t, const IgemmCall& c, long m_begin, long m_end, float* stats) {
+    switch (t) {
+        case T_212: return launch_igemm<2, 1, 2, BF>(c, m_begin, m_end, stats);
+        case T_124: return launch_igemm<1, 2, 4, BF>(c, m_begin, m_end, stats);
+        case T_222: return launch_igemm<2, 2, 2, BF>(c, m_begin, m_end, stats);
+        case T_114: return launch_igemm<1, 1, 4, BF>(c, m_begin, m_end, stats);
+        case T_122: return launch_igemm<1, 2, 2, BF>(c, m_begin, m_end, stats);
+        default: return launch_igemm<1, 1, 2, BF>(c, m_begin, m_end, stats);
     }
-    if (bf) {   // bf16-operand variants of the same tile shapes
-        if (g.Cout <= 64) return launch_igemm<2, 1, 2, 1>(x, ldx, w, bias, y, ldy, g, 0, M, stream, stats, pivot, batch, zx, zw, zy);
-        int rc = launch_igemm<1, 2, 4, 1>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy);
-        if (rc || p.nblk_tail == 0) return rc;
-        float* st = stats ? stats + (long)p.nblk_body * 2 * g.Cout : nullptr;
-        // (the plan counts a tail_tm == 4 tail in 128-row blocks: the launch must have that BM, or the statistics overrun the plan)
-        if (p.tail_tm == 4) return launch_igemm<1, 1, 4, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
-        if (p.tail_tm == 2) return launch_igemm<2, 2, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
-        if (p.tail_tn == 2) return launch_igemm<1, 2, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
-        return launch_igemm<1, 1, 2, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy);
-    }
-    if (g.Cout <= 64) return launch_igemm<2, 1>(x, ldx, w, bias, y, ldy, g, 0, M, stream, stats, pivot, batch, zx, zw, zy, epi);
-    // 128x128 body tiles are computed by 8 waves (4x2, 32x64 outputs each; 4 waves per SIMD with two resident
-    // blocks): +6 % MFMA throughput over 4 waves of 64x64 (98.7 -> 104.6 TFLOP/s on the step's launch mix; more
-    // waves cover each other's LDS / barrier stalls).  U2PL_IGEMM_WAVES=4 selects the older shape.
+}
+// 128x128 body tiles are computed by 8 waves (4x2, 32x64 outputs each; 4 waves per SIMD with two resident
+// blocks): +6 % MFMA throughput over 4 waves of 64x64 (98.7 -> 104.6 TFLOP/s on the step's launch mix; more
+// waves cover each other's LDS / barrier stalls).  U2PL_IGEMM_WAVES=4 selects the older shape.
+static int igemm_waves() {
     static int waves = 0;
     if (!waves) { const char* e = getenv("U2PL_IGEMM_WAVES"); waves = (e && atoi(e) == 4) ? 4 : 8; }
-    int rc = waves == 8 ? launch_igemm<1, 2, 4>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy, epi)
-                        : launch_igemm<2, 2>(x, ldx, w, bias, y, ldy, g, 0, p.m_body, stream, stats, pivot, batch, zx, zw, zy, epi);
+    return waves;
+}
+// the ladder: Cout <= 64 in one launch; otherwise the body, then the planner's tail with its statistics behind the body's.
+// BF: 0 the fp32 instruction, 3 six bf16 piece products, 1 bf16-rounded operands.
+template <int BF>
+static int run_igemm_bf(const IgemmCall& c) {
+    const ConvGeom& g = c.g;
+    // (BF == 1 never carries an epilogue)
+    if (c.epi.mean && (BF == 1 || c.stats || c.batch != 1 || (g.Cout & 3))) return U2PL_EINVAL;
+    const long M = geom_rows_out(g);
+    const IgemmPlan p = plan_igemm(g, c.batch);
+    if (g.Cout <= 64) return launch_igemm_tile<BF>(T_212, c, 0, M, c.stats);
+    // (BF == 1 ignores U2PL_IGEMM_WAVES: its body is the 8-wave shape)
+    const int rc = launch_igemm_tile<BF>(BF != 1 && igemm_waves() == 4 ? T_222 : T_124, c, 0, p.m_body, c.stats);
     if (rc || p.nblk_tail == 0) return rc;
-    float* st = stats ? stats + (long)p.nblk_body * 2 * g.Cout : nullptr;
-    if (p.tail_tm == 4) return launch_igemm<1, 1, 4>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-    if (p.tail_tm == 2) return launch_igemm<2, 2>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-    if (p.tail_tn == 2) return launch_igemm<1, 2>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
-    return launch_igemm<1, 1>(x, ldx, w, bias, y, ldy, g, p.m_body, M, stream, st, pivot, batch, zx, zw, zy, epi);
+    // (the plan counts a tail_tm == 4 tail in 128-row blocks: the launch must have that BM, or the statistics overrun the plan)
+    const IgemmTile tail = p.tail_tm == 4 ? T_114 : p.tail_tm == 2 ? T_222 : p.tail_tn == 2 ? T_122 : T_112;
+    return launch_igemm_tile<BF>(tail, c, p.m_body, M, c.stats ? c.stats + (long)p.nblk_body * 2 * g.Cout : nullptr);
+}
+static int run_igemm(const IgemmCall& c, bool bf16op = false) {
+    if (!geom_ok(c.g) || c.g.Cin % BK) return U2PL_EINVAL;
+    if (bf16op) return run_igemm_bf<1>(c);
+    return conv_split() ? run_igemm_bf<3>(c) : run_igemm_bf<0>(c);
 }
 
 // batch independent row-major GEMMs  Y_z[M][Nn] = X_z[M][K] * W_z[Nn][K]^T  (the Winograd component products)
@@ -490,16 +489,16 @@ U2PL_API int u2pl_gemm_batched_f32(const float* x, long ldx, long zx, const floa
                                    long zy, long M, int K, int Nn, int batch, hipStream_t stream) {
     if (M <= 0 || batch <= 0) return 0;
     if (M >= (1L << 31)) return U2PL_EINVAL;
-    ConvGeom g = {1, (int)M, 1, K, (int)M, 1, Nn, 1, 1, 1, 0, 0, 1, 0};
-    return run_igemm(x, ldx, w, nullptr, y, ldy, g, stream, nullptr, nullptr, batch, zx, zw, zy);
+    IgemmCall c = igemm_call(x, ldx, w, nullptr, y, ldy, geom_gemm(M, K, Nn), stream);
+    c.batch = batch; c.zx = zx; c.zw = zw; c.zy = zy;
+    return run_igemm(c);
 }
 
 // nn.Conv2d forward: resnet.py:25-41,178-186; base.py:23-83; decoder.py:60-106,132-138
 U2PL_API int u2pl_conv2d_fwd_f32(const float* x, long ldx, const float* w, const float* bias, float* y,
                                  long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
                                  int R, int S, int stride, int pad, int dil, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm(x, ldx, w, bias, y, ldy, g, stream);
+    return run_igemm(igemm_call(x, ldx, w, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
 }
 
 // forward fused with the eval-mode BatchNorm (+residual, ReLU) that follows it (teacher pseudo-label pass, validate(),
@@ -510,59 +509,50 @@ U2PL_API int u2pl_conv2d_fwd_bnact_f32(const float* x, long ldx, const float* w,
                                        const float* invstd, const float* gamma, const float* beta, const float* res,
                                        long ldr, int relu, hipStream_t stream) {
     if (!mean || !invstd || !gamma || !beta || (Cout & 3) || (res && (ldr & 3))) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    const BnEpi epi = {mean, invstd, gamma, beta, res, ldr, relu};
-    return run_igemm(x, ldx, w, bias, y, ldy, g, stream, nullptr, nullptr, 1, 0, 0, 0, 0, &epi);
+    IgemmCall c = igemm_call(x, ldx, w, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream);
+    c.epi = BnEpi{mean, invstd, gamma, beta, res, ldr, relu};
+    return run_igemm(c);
 }
 
 // forward fused with the BatchNorm statistics of its output (train-mode conv -> BN pairs): also writes the
 // per-tile pivot-shifted column sums [nblk][2][Cout] (nblk = u2pl_conv2d_fwd_stat_blocks) to stats_partial
 U2PL_API int u2pl_conv2d_fwd_stat_blocks(int N, int Hout, int Wout, int Cout) {
-    ConvGeom g = {N, 0, 0, 32, Hout, Wout, Cout, 1, 1, 1, 0, 0, 1, 0};
-    const IgemmPlan p = plan_igemm(g);
+    const IgemmPlan p = plan_igemm(geom_query(N, Hout, Wout, 32, Cout, 1, 1));
     return p.nblk_body + p.nblk_tail;
 }
 U2PL_API int u2pl_conv2d_fwd_bnstats_f32(const float* x, long ldx, const float* w, const float* bias, float* y,
                                          long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
                                          int R, int S, int stride, int pad, int dil, const float* pivot,
                                          float* stats_partial, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm(x, ldx, w, bias, y, ldy, g, stream, stats_partial, pivot);
+    return run_igemm(igemm_call(x, ldx, w, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream,
+                                stats_partial, pivot));
 }
 
 // the same three products with bf16-rounded operands on the bf16 matrix cores (fp32 accumulate / fp32 tensors)
 U2PL_API int u2pl_conv2d_fwd_bf16op_f32(const float* x, long ldx, const float* w, const float* bias, float* y,
                                         long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
                                         int R, int S, int stride, int pad, int dil, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm(x, ldx, w, bias, y, ldy, g, stream, nullptr, nullptr, 1, 0, 0, 0, 1);
+    return run_igemm(igemm_call(x, ldx, w, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream), true);
 }
 U2PL_API int u2pl_conv2d_fwd_bnstats_bf16op_f32(const float* x, long ldx, const float* w, const float* bias, float* y,
                                                 long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout,
                                                 int Cout, int R, int S, int stride, int pad, int dil,
                                                 const float* pivot, float* stats_partial, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm(x, ldx, w, bias, y, ldy, g, stream, stats_partial, pivot, 1, 0, 0, 0, 1);
-}
-U2PL_API int u2pl_conv2d_dgrad_bf16op_f32(const float* dy, long lddy, const float* wT, float* dx, long lddx, int N,
-                                          int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S,
-                                          int stride, int pad, int dil, hipStream_t stream) {
-    int l2 = log2_exact(stride);
-    if (l2 < 0) return U2PL_EINVAL;
-    ConvGeom g = {N, Hout, Wout, Cout, Hin, Win, Cin, R, S, 1, pad, pad, -dil, l2};
-    return run_igemm(dy, lddy, wT, nullptr, dx, lddx, g, stream, nullptr, nullptr, 1, 0, 0, 0, 1);
+    return run_igemm(igemm_call(x, ldx, w, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream,
+                                stats_partial, pivot), true);
 }
 
 // data gradient: dX[n,hi,wi,ci] = sum_{r,s,co} dY[n,(hi+pad-r*dil)/st,(wi+pad-s*dil)/st,co] * W[co][r][s][ci]
 // wT = weights transposed to [Cin][R][S][Cout] (u2pl_weight_transpose_f32)
+U2PL_API int u2pl_conv2d_dgrad_bf16op_f32(const float* dy, long lddy, const float* wT, float* dx, long lddx, int N,
+                                          int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S,
+                                          int stride, int pad, int dil, hipStream_t stream) {
+    return run_igemm(igemm_call(dy, lddy, wT, nullptr, dx, lddx, geom_dgrad(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream), true);
+}
 U2PL_API int u2pl_conv2d_dgrad_f32(const float* dy, long lddy, const float* wT, float* dx, long lddx, int N,
                                    int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S,
                                    int stride, int pad, int dil, hipStream_t stream) {
-    int l2 = log2_exact(stride);
-    if (l2 < 0) return U2PL_EINVAL;
-    // roles swap: the "input" of the gather is dY (Hout x Wout x Cout), the output is dX
-    ConvGeom g = {N, Hout, Wout, Cout, Hin, Win, Cin, R, S, 1, pad, pad, -dil, l2};
-    return run_igemm(dy, lddy, wT, nullptr, dx, lddx, g, stream);
+    return run_igemm(igemm_call(dy, lddy, wT, nullptr, dx, lddx, geom_dgrad(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
 }
 
 // [A][T][B] -> [B][T][A]   (A = Cout, T = R*S, B = Cin)
@@ -896,29 +886,37 @@ __global__ void k_wgrad_reduce(const float* __restrict__ part, long wsz, int nsp
     }
 }
 
-static void wgrad_plan(const ConvGeom& g, int BM, int BN, int& ctiles, int& nsplit, int& cps) {
-    const long M = (long)g.N * g.Hout * g.Wout;
-    const long nchunks = (M + BK - 1) / BK;
-    ctiles = cdiv(g.Cin, BN);
+static WgradSlabs wgrad_plan(const ConvGeom& g, int BM, int BN) {
+    const long nchunks = (geom_rows_out(g) + BK - 1) / BK;
+    const int ctiles = cdiv(g.Cin, BN);
     const long tiles = (long)cdiv(g.Cout, BM) * ctiles * g.R * g.S;
     long want = (1024 + tiles - 1) / tiles;          // aim for >= 1024 blocks (2 per CU x 2 rounds)
     long maxsplit = (nchunks + 7) / 8;               // >= 8 chunks (256 pixels) per split
     if (want > maxsplit) want = maxsplit;
     if (want < 1) want = 1;
-    cps = (int)((nchunks + want - 1) / want);
-    nsplit = (int)((nchunks + cps - 1) / cps);
+    const int cps = (int)((nchunks + want - 1) / want);
+    return WgradSlabs{ctiles, (int)((nchunks + cps - 1) / cps), cps};
+}
+
+// Which kernel family a weight gradient runs on and which slab plan it gets, from the geometry (taps = R * S) and the arithmetic:
+// the fp32 matrix instruction (k_conv_wgrad), six bf16 piece products (k_wgrad_tr where it serves the layer, else k_conv_wgrad_bf16
+// SP == 3), split-fp16 with operand maxima (k_wgrad_tr only, under the split switch) or bf16-rounded operands (k_conv_wgrad_bf16 SP == 1)
+enum WgradArith { WG_FP32, WG_SIX, WG_H, WG_BF16OP };
+enum WgradFamily { WGK_NONE, WGK_F32, WGK_BF16_SIX, WGK_BF16_OP, WGK_TR };
+struct WgradChoice { WgradFamily family; int BM, BN; WgradSlabs slabs; };
+static WgradArith wgrad_default_arith() { return conv_split() ? WG_SIX : WG_FP32; }
+static WgradChoice wgrad_select(const ConvGeom& g, WgradArith arith) {
+    const int BM = g.Cout > 64 ? 128 : 64, BN = g.Cin > 64 ? 128 : 64;
+    if ((arith == WG_SIX || (arith == WG_H && conv_split())) && wgrad_tr_eligible(g)) return WgradChoice{WGK_TR, 128, 0, wgrad_tr_plan(g)};
+    if (arith == WG_H) return WgradChoice{WGK_NONE, 0, 0, WgradSlabs{0, 0, 0}};
+    return WgradChoice{arith == WG_SIX ? WGK_BF16_SIX : arith == WG_BF16OP ? WGK_BF16_OP : WGK_F32, BM, BN, wgrad_plan(g, BM, BN)};
 }
 
 U2PL_API size_t u2pl_conv2d_wgrad_workspace_bytes(int N, int Hout, int Wout, int Cin, int Cout, int R, int S) {
-    ConvGeom g = {N, 0, 0, Cin, Hout, Wout, Cout, R, S, 1, 0, 0, 1, 0};
-    int ct, ns, cps;
-    wgrad_plan(g, Cout > 64 ? 128 : 64, Cin > 64 ? 128 : 64, ct, ns, cps);
-    if (wgrad_tr_eligible(g)) {      // (the larger of the two kernels' plans: the arithmetic switch may change between query and launch)
-        int ct2, ns2, cps2;
-        wgrad_tr_plan(g, R * S, ct2, ns2, cps2);
-        if (ns2 > ns) ns = ns2;
-    }
-    return (size_t)ns * Cout * R * S * Cin * sizeof(float);
+    const ConvGeom g = geom_query(N, Hout, Wout, Cin, Cout, R, S);
+    // (the larger of the two kernels' plans: the arithmetic switch may change between query and launch)
+    const int ns = wgrad_select(g, WG_FP32).slabs.nsplit, ns2 = wgrad_select(g, WG_SIX).slabs.nsplit;
+    return (size_t)(ns2 > ns ? ns2 : ns) * Cout * R * S * Cin * sizeof(float);
 }
 
 // U2PL_WGRAD_WAVES = 8 (default) | 4: block shape of the 128x128 weight-gradient tile (A/B switch; same results)
@@ -930,9 +928,18 @@ static int wgrad_waves() {
     }
     return v;
 }
+// the launch both kernel templates of this file share: extents, grid (Cin tiles x taps, Cout tiles of BM rows, slabs)
+typedef void (*WgradKernel)(const float*, long, const float*, long, float*, ConvGeom, int, int, unsigned, unsigned, long, long);
+static int launch_wgrad_kernel(WgradKernel kern, int BM, int threads, size_t lds, const WgradCall& c, const WgradSlabs& s) {
+    unsigned dyb, xb;
+    if (!wgrad_extents(c, dyb, xb)) return U2PL_EINVAL;
+    dim3 grid((unsigned)(s.ctiles * c.g.R * c.g.S), (unsigned)cdiv(c.g.Cout, BM), (unsigned)s.nsplit);
+    U2PL_LAUNCH(kern, grid, dim3(threads), lds, c.stream, c.dy, c.lddy, c.x, c.ldx, c.part, c.g, s.ctiles, s.cps, dyb, xb, c.zdy, c.zx);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
 template <int TM, int TN, int WM = 2>
-static int launch_wgrad(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g,
-                        int ctiles, int nsplit, int cps, hipStream_t stream, long zdy = 0, long zx = 0) {
+static int launch_wgrad(const WgradCall& c, const WgradSlabs& s) {
     constexpr int BM = 32 * TM * WM, BN = 64 * TN;
     const size_t lds = (size_t)2 * BK * (BM + 4 + BN + 4) * sizeof(float);
     static bool attr_set = false;
@@ -940,85 +947,70 @@ static int launch_wgrad(const float* dy, long lddy, const float* x, long ldx, fl
         (void)hipFuncSetAttribute((const void*)k_conv_wgrad<TM, TN, WM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    const long dyb = (((long)g.N * g.Hout * g.Wout - 1) * lddy + g.Cout) * 4;
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    if (dyb >= (1L << 31) || xb >= (1L << 31)) return U2PL_EINVAL;
-    dim3 grid((unsigned)(ctiles * g.R * g.S), (unsigned)cdiv(g.Cout, BM), (unsigned)nsplit);
-    U2PL_LAUNCH((k_conv_wgrad<TM, TN, WM>), grid, dim3(128 * WM), lds, stream, dy, lddy, x, ldx, part, g, ctiles, cps,
-                       (unsigned)dyb, (unsigned)xb, zdy, zx);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    return launch_wgrad_kernel(k_conv_wgrad<TM, TN, WM>, BM, 128 * WM, lds, c, s);
 }
-
-template <int TM, int TN, int SP = 1>
-static int launch_wgrad_bf16(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g,
-                             int ctiles, int nsplit, int cps, hipStream_t stream, long zdy = 0, long zx = 0) {
+template <int TM, int TN, int SP>
+static int launch_wgrad_bf16(const WgradCall& c, const WgradSlabs& s) {
     constexpr int BM = 64 * TM, BN = 64 * TN;
     const size_t lds = (size_t)(SP == 3 ? 3 : 2) * (BM + BN) * LDPW * sizeof(unsigned short);
-    const long dyb = (((long)g.N * g.Hout * g.Wout - 1) * lddy + g.Cout) * 4;
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    if (dyb >= (1L << 31) || xb >= (1L << 31)) return U2PL_EINVAL;
-    dim3 grid((unsigned)(ctiles * g.R * g.S), (unsigned)cdiv(g.Cout, BM), (unsigned)nsplit);
-    U2PL_LAUNCH((k_conv_wgrad_bf16<TM, TN, SP>), grid, dim3(256), lds, stream, dy, lddy, x, ldx, part, g, ctiles, cps,
-                       (unsigned)dyb, (unsigned)xb, zdy, zx);
+    return launch_wgrad_kernel(k_conv_wgrad_bf16<TM, TN, SP>, BM, 256, lds, c, s);
+}
+// the 128 / 64 tile switch of each kernel template
+static int launch_wgrad_f32_tile(const WgradCall& c, const WgradChoice& k) {
+    if (k.BM == 128 && k.BN == 128) return wgrad_waves() == 8 ? launch_wgrad<1, 2, 4>(c, k.slabs) : launch_wgrad<2, 2>(c, k.slabs);
+    if (k.BM == 128) return launch_wgrad<2, 1>(c, k.slabs);
+    if (k.BN == 128) return launch_wgrad<1, 2>(c, k.slabs);
+    return launch_wgrad<1, 1>(c, k.slabs);
+}
+template <int SP>
+static int launch_wgrad_bf16_tile(const WgradCall& c, const WgradChoice& k) {
+    if (k.BM == 128 && k.BN == 128) return launch_wgrad_bf16<2, 2, SP>(c, k.slabs);
+    if (k.BM == 128) return launch_wgrad_bf16<2, 1, SP>(c, k.slabs);
+    if (k.BN == 128) return launch_wgrad_bf16<1, 2, SP>(c, k.slabs);
+    return launch_wgrad_bf16<1, 1, SP>(c, k.slabs);
+}
+// the slabs of one call into c.part; dw != NULL: then dW = (accumulate ? dW : 0) + the slabs in order
+static int run_wgrad(const WgradCall& c, WgradArith arith, float* dw = nullptr, int accumulate = 0) {
+    const ConvGeom& g = c.g;
+    const WgradChoice k = wgrad_select(g, arith);
+    int rc = U2PL_EINVAL;
+    switch (k.family) {
+        case WGK_NONE: break;
+        case WGK_TR: rc = launch_wgrad_tr(c, k.slabs); break;
+        case WGK_BF16_SIX: rc = launch_wgrad_bf16_tile<3>(c, k); break;
+        case WGK_BF16_OP: rc = launch_wgrad_bf16_tile<1>(c, k); break;
+        case WGK_F32: rc = launch_wgrad_f32_tile(c, k); break;
+    }
+    if (rc || !dw) return rc;
+    const long wsz = (long)g.Cout * g.R * g.S * g.Cin;
+    U2PL_LAUNCH(k_wgrad_reduce, dim3(grid_for(wsz / 4, 256)), dim3(256), 0, c.stream, c.part, wsz, k.slabs.nsplit, accumulate, dw);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
+static WgradCall wgrad_call(const float* dy, long lddy, const float* x, long ldx, void* part, const ConvGeom& g, hipStream_t stream,
+                            const float* dy_amax = nullptr, const float* x_amax = nullptr, long zdy = 0, long zx = 0) {
+    return WgradCall{dy, lddy, x, ldx, (float*)part, g, stream, zdy, zx, dy_amax, x_amax};
+}
+
 // weight gradient of nn.Conv2d (autograd of the reference's loss.backward(), train_semi.py:527)
 U2PL_API int u2pl_conv2d_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, float* dw,
                                    void* workspace, int accumulate, int N, int Hin, int Win, int Cin, int Hout,
                                    int Wout, int Cout, int R, int S, int stride, int pad, int dil,
                                    hipStream_t stream) {
     if (Cin % 4 || Cout % 4) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    const int BM = Cout > 64 ? 128 : 64, BN = Cin > 64 ? 128 : 64;
-    int ct, ns, cps;
-    wgrad_plan(g, BM, BN, ct, ns, cps);
-    float* part = (float*)workspace;
-    int rc;
-    if (conv_split() && wgrad_tr_eligible(g)) {
-        wgrad_tr_plan(g, R * S, ct, ns, cps);
-        rc = launch_wgrad_tr(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, 0, 0);
-    } else if (conv_split()) {
-        if (BM == 128 && BN == 128) rc = launch_wgrad_bf16<2, 2, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-        else if (BM == 128) rc = launch_wgrad_bf16<2, 1, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-        else if (BN == 128) rc = launch_wgrad_bf16<1, 2, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-        else rc = launch_wgrad_bf16<1, 1, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    }
-    else if (BM == 128 && BN == 128)
-        rc = wgrad_waves() == 8 ? launch_wgrad<1, 2, 4>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream)
-                                : launch_wgrad<2, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else if (BM == 128) rc = launch_wgrad<2, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else if (BN == 128) rc = launch_wgrad<1, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else rc = launch_wgrad<1, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    if (rc) return rc;
-    const long wsz = (long)Cout * R * S * Cin;
-    U2PL_LAUNCH(k_wgrad_reduce, dim3(grid_for(wsz / 4, 256)), dim3(256), 0, stream, part, wsz, ns, accumulate, dw);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    const ConvGeom g = geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil);
+    return run_wgrad(wgrad_call(dy, lddy, x, ldx, workspace, g, stream), wgrad_default_arith(), dw, accumulate);
 }
 
 // split-fp16 weight gradient (round 6; conv_geom.h, wgrad_tr.hip): dy_amax / x_amax = device scalars max |dY|, max |X| (or upper
 // bounds within ~2^8).  Only the layers k_wgrad_tr serves (u2pl_wgrad_h_eligible); workspace / slab plan as u2pl_conv2d_wgrad_f32.
-U2PL_API int u2pl_wgrad_h_eligible(int Cin, int Cout) {
-    ConvGeom g = {1, 1, 1, Cin, 1, 1, Cout, 1, 1, 1, 0, 0, 1, 0};
-    return conv_split() && wgrad_tr_eligible(g);
-}
+U2PL_API int u2pl_wgrad_h_eligible(int Cin, int Cout) { return wgrad_select(geom_gemm(1, Cin, Cout), WG_H).family != WGK_NONE; }
 U2PL_API int u2pl_conv2d_wgrad_h_f32(const float* dy, long lddy, const float* dy_amax, const float* x, long ldx, const float* x_amax,
                                      float* dw, void* workspace, int accumulate, int N, int Hin, int Win, int Cin, int Hout,
                                      int Wout, int Cout, int R, int S, int stride, int pad, int dil, hipStream_t stream) {
     if (Cin % 4 || Cout % 4 || !dy_amax || !x_amax) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    if (!(conv_split() && wgrad_tr_eligible(g))) return U2PL_EINVAL;
-    int ct, ns, cps;
-    wgrad_tr_plan(g, R * S, ct, ns, cps);
-    float* part = (float*)workspace;
-    const int rc = launch_wgrad_tr(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, 0, 0, dy_amax, x_amax);
-    if (rc) return rc;
-    const long wsz = (long)Cout * R * S * Cin;
-    U2PL_LAUNCH(k_wgrad_reduce, dim3(grid_for(wsz / 4, 256)), dim3(256), 0, stream, part, wsz, ns, accumulate, dw);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    const ConvGeom g = geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil);
+    return run_wgrad(wgrad_call(dy, lddy, x, ldx, workspace, g, stream, dy_amax, x_amax), WG_H, dw, accumulate);
 }
 
 // weight gradient with bf16-rounded dY / X operands (fp32 accumulate); workspace as u2pl_conv2d_wgrad_workspace_bytes
@@ -1027,36 +1019,14 @@ U2PL_API int u2pl_conv2d_wgrad_bf16op_f32(const float* dy, long lddy, const floa
                                           int Wout, int Cout, int R, int S, int stride, int pad, int dil,
                                           hipStream_t stream) {
     if (Cin % 4 || Cout % 4) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    const int BM = Cout > 64 ? 128 : 64, BN = Cin > 64 ? 128 : 64;
-    int ct, ns, cps;
-    wgrad_plan(g, BM, BN, ct, ns, cps);
-    float* part = (float*)workspace;
-    int rc;
-    if (BM == 128 && BN == 128) rc = launch_wgrad_bf16<2, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else if (BM == 128) rc = launch_wgrad_bf16<2, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else if (BN == 128) rc = launch_wgrad_bf16<1, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    else rc = launch_wgrad_bf16<1, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream);
-    if (rc) return rc;
-    const long wsz = (long)Cout * R * S * Cin;
-    U2PL_LAUNCH(k_wgrad_reduce, dim3(grid_for(wsz / 4, 256)), dim3(256), 0, stream, part, wsz, ns, accumulate, dw);
-    U2PL_LAUNCH_CHECK();
-    return 0;
+    const ConvGeom g = geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil);
+    return run_wgrad(wgrad_call(dy, lddy, x, ldx, workspace, g, stream), WG_BF16OP, dw, accumulate);
 }
 
 // batch independent weight-gradient GEMMs  P_z[Cout][Cin] = dY_z[M][Cout]^T * X_z[M][Cin]  (Winograd components;
 // reduction over the M tile rows, split into slabs like the direct wgrad).  part: [nsplit][Cout][batch][Cin]
-static ConvGeom batched_wgrad_geom(long M, int Cin, int Cout, int batch) {
-    // identity gather for every "tap": step = 0, offsets 0
-    ConvGeom g = {1, (int)M, 1, Cin, (int)M, 1, Cout, batch, 1, 1, 0, 0, 0, 0};
-    return g;
-}
 U2PL_API int u2pl_wgrad_batched_splits(long M, int Cin, int Cout, int batch) {
-    ConvGeom g = batched_wgrad_geom(M, Cin, Cout, batch);
-    int ct, ns, cps;
-    if (conv_split() && wgrad_tr_eligible(g)) wgrad_tr_plan(g, batch, ct, ns, cps);
-    else wgrad_plan(g, Cout > 64 ? 128 : 64, Cin > 64 ? 128 : 64, ct, ns, cps);
-    return ns;
+    return wgrad_select(geom_wgrad_batched(M, Cin, Cout, batch), wgrad_default_arith()).slabs.nsplit;
 }
 U2PL_API size_t u2pl_wgrad_batched_workspace_bytes(long M, int Cin, int Cout, int batch) {
     return (size_t)u2pl_wgrad_batched_splits(M, Cin, Cout, batch) * Cout * batch * Cin * sizeof(float);
@@ -1064,37 +1034,15 @@ U2PL_API size_t u2pl_wgrad_batched_workspace_bytes(long M, int Cin, int Cout, in
 U2PL_API int u2pl_wgrad_batched_f32(const float* dy, long lddy, long zdy, const float* x, long ldx, long zx,
                                     float* part, long M, int Cin, int Cout, int batch, hipStream_t stream) {
     if (Cin % 4 || Cout % 4 || M <= 0 || M >= (1L << 31)) return U2PL_EINVAL;
-    ConvGeom g = batched_wgrad_geom(M, Cin, Cout, batch);
-    const int BM = Cout > 64 ? 128 : 64, BN = Cin > 64 ? 128 : 64;
-    int ct, ns, cps;
-    if (conv_split() && wgrad_tr_eligible(g)) {
-        wgrad_tr_plan(g, batch, ct, ns, cps);
-        return launch_wgrad_tr(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-    }
-    wgrad_plan(g, BM, BN, ct, ns, cps);
-    if (conv_split()) {
-        if (BM == 128 && BN == 128) return launch_wgrad_bf16<2, 2, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-        if (BM == 128) return launch_wgrad_bf16<2, 1, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-        if (BN == 128) return launch_wgrad_bf16<1, 2, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-        return launch_wgrad_bf16<1, 1, 3>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-    }
-    if (BM == 128 && BN == 128)
-        return wgrad_waves() == 8 ? launch_wgrad<1, 2, 4>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx)
-                                  : launch_wgrad<2, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-    if (BM == 128) return launch_wgrad<2, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-    if (BN == 128) return launch_wgrad<1, 2>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
-    return launch_wgrad<1, 1>(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx);
+    return run_wgrad(wgrad_call(dy, lddy, x, ldx, part, geom_wgrad_batched(M, Cin, Cout, batch), stream, nullptr, nullptr, zdy, zx),
+                     wgrad_default_arith());
 }
 
 // split-fp16 form of u2pl_wgrad_batched_f32 (same slab plan and workspace; u2pl_wgrad_h_eligible(Cin, Cout) layers only)
 U2PL_API int u2pl_wgrad_batched_h_f32(const float* dy, long lddy, long zdy, const float* dy_amax, const float* x, long ldx, long zx,
                                       const float* x_amax, float* part, long M, int Cin, int Cout, int batch, hipStream_t stream) {
     if (Cin % 4 || Cout % 4 || M <= 0 || M >= (1L << 31) || !dy_amax || !x_amax) return U2PL_EINVAL;
-    ConvGeom g = batched_wgrad_geom(M, Cin, Cout, batch);
-    if (!(conv_split() && wgrad_tr_eligible(g))) return U2PL_EINVAL;
-    int ct, ns, cps;
-    wgrad_tr_plan(g, batch, ct, ns, cps);
-    return launch_wgrad_tr(dy, lddy, x, ldx, part, g, ct, ns, cps, stream, zdy, zx, dy_amax, x_amax);
+    return run_wgrad(wgrad_call(dy, lddy, x, ldx, part, geom_wgrad_batched(M, Cin, Cout, batch), stream, dy_amax, x_amax, zdy, zx), WG_H);
 }
 
 // ---------------------------------------------------------------------------
@@ -1126,7 +1074,7 @@ __global__ void k_im2col(const float* __restrict__ x, long ldx, float* __restric
 }
 U2PL_API int u2pl_im2col_f32(const float* x, long ldx, float* col, int Kp, int N, int Hin, int Win, int Cin,
                              int Hout, int Wout, int R, int S, int stride, int pad, int dil, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, 0, R, S, stride, -pad, -pad, dil, 0};
+    const ConvGeom g = geom_fwd(N, Hin, Win, Cin, Hout, Wout, 0, R, S, stride, pad, dil);
     const long total = (long)N * Hout * Wout * Kp;
     U2PL_LAUNCH(k_im2col, dim3(grid_for(total, 256, 1 << 16)), dim3(256), 0, stream, x, ldx, col, g, Kp);
     U2PL_LAUNCH_CHECK();

@@ -122,3 +122,33 @@ __device__ __forceinline__ void split2_f16(float4 v, float s, uint2& p0, uint2& 
     p0 = make_uint2(split2_first(v.x, v.y, s), split2_first(v.z, v.w, s));
     p1 = make_uint2(split2_second(v.x, v.y, s, p0.x), split2_second(v.z, v.w, s, p0.y));
 }
+
+// ---- host side: every ConvGeom is built here, and so is every buffer extent --------------------------------------------------------
+// forward: gather o * stride - pad + r * dil
+static inline ConvGeom geom_fwd(int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil) {
+    return ConvGeom{N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
+}
+// data gradient: the roles swap (the gathered tensor is dY, Hout x Wout x Cout; the output is dX), gather (i + pad - r * dil) >> log2(stride)
+// with a divisibility test.  A stride that is no power of two gives log2div = -1, which geom_ok reports and every GEMM entry refuses.
+static inline ConvGeom geom_dgrad(int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil) {
+    int l2 = 0;
+    while ((1 << l2) < stride) ++l2;
+    return ConvGeom{N, Hout, Wout, Cout, Hin, Win, Cin, R, S, 1, pad, pad, -dil, (1 << l2) == stride ? l2 : -1};
+}
+static inline bool geom_ok(const ConvGeom& g) { return g.log2div >= 0; }
+// row-major GEMM Y[M][Nn] = X[M][K] W[Nn][K]^T (one matrix of a batch): a 1x1 forward over an M x 1 map.  Also the geometry of the
+// queries that only need channel counts.
+static inline ConvGeom geom_gemm(long M, int K, int Nn) { return geom_fwd(1, (int)M, 1, K, (int)M, 1, Nn, 1, 1, 1, 0, 1); }
+// batch of weight-gradient GEMMs P_z[Cout][Cin] = dY_z[M][Cout]^T X_z[M][Cin]: the components are the "taps" (R = batch) of an identity
+// gather (step = 0, offsets 0)
+static inline ConvGeom geom_wgrad_batched(long M, int Cin, int Cout, int batch) { return geom_fwd(1, (int)M, 1, Cin, (int)M, 1, Cout, batch, 1, 1, 0, 0); }
+// a planner query: output pixels and channel counts only, no input map
+static inline ConvGeom geom_query(int N, int Hout, int Wout, int Cin, int Cout, int R, int S) { return geom_fwd(N, 0, 0, Cin, Hout, Wout, Cout, R, S, 1, 0, 1); }
+// bytes spanned by `rows` rows of pitch `ld` floats with `cols` columns in the last one; false at 2 GiB (raw-buffer descriptors, 32-bit offsets)
+static inline bool span_bytes(long rows, long ld, long cols, unsigned& bytes) {
+    const long b = ((rows - 1) * ld + cols) * 4;
+    bytes = (unsigned)b;
+    return b < (1L << 31);
+}
+static inline long geom_rows_in(const ConvGeom& g) { return (long)g.N * g.Hin * g.Win; }
+static inline long geom_rows_out(const ConvGeom& g) { return (long)g.N * g.Hout * g.Wout; }

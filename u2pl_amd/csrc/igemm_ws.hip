@@ -739,73 +739,78 @@ static int ws_persist() {
     return g_ws_persist;
 }
 U2PL_API int u2pl_igemm_ws_set_persist(int on) { const int old = ws_persist(); g_ws_persist = on != 0; return old; }
+
+// one call of the pre-split GEMM, filled once by the entry point.  x_amax == NULL: the bf16 three-piece planes of u2pl_weight_split3_f32
+// (six products); x_amax != NULL: split-fp16 -- the planes of u2pl_weight_split2h_f32 and the device scalar max |x| of the activation
+// operand (three products).  batch > 1: independent GEMMs zx / zy floats apart; epi.mean == NULL: no eval-BatchNorm epilogue.
+struct WsCall {
+    const float* x; long ldx; const float* x_amax; const void* ws; const float* bias; float* y; long ldy; ConvGeom g; hipStream_t stream;
+    float* stats; const float* pivot; int batch; long zx, zy; BnEpi epi;
+};
+// what every launch of a call hands its kernel besides the call itself: padded weight rows, byte extents of ONE matrix of the batch, the
+// weight maxima behind the planes (split-fp16)
+struct WsExtents { int Np; unsigned xb, wsb1, yb, resb; const unsigned* b_amax; };
+template <int NP>
+static int ws_extents(const WsCall& c, WsExtents& e) {
+    const ConvGeom& g = c.g;
+    const long M = geom_rows_out(g);
+    e.Np = ws_pad_rows(g.Cout);
+    const long wsb1 = (long)(g.R * g.S * g.Cin / 32) * NP * e.Np * WS_ROW_B;          // one matrix
+    e.wsb1 = (unsigned)wsb1;
+    e.b_amax = (const unsigned*)((const char*)c.ws + (size_t)c.batch * wsb1);       // split-fp16: behind the planes
+    // every MATRIX of the batch within 2 GiB (32-bit byte offsets inside a matrix); the batch itself may be larger: the kernel
+    // rebuilds the buffer descriptors per matrix from a 64-bit base (x + z * zx, ws + z * zws, y + z * zy)
+    if (!span_bytes(geom_rows_in(g), c.ldx, g.Cin, e.xb) || wsb1 >= (1L << 31) || !span_bytes(M, c.ldy, g.Cout, e.yb)) return U2PL_EINVAL;
+    e.resb = 0;
+    if (c.epi.res && !span_bytes(M, c.epi.ldr, g.Cout, e.resb)) return U2PL_EINVAL;
+    return 0;
+}
+
+// tiles [tile_first, tile_first + tile_count) of one tile shape (tile_count < 0: all of them)
 template <int TM, int TN, int WM, int WN, bool PW, int ABL = 0, int NP = 3>
-static int launch_igemm_ws(const float* x, long ldx, const float* x_amax, const void* ws, const float* bias, float* y, long ldy,
-                           const ConvGeom& g, hipStream_t stream, float* stats, const float* pivot, int batch, long zx,
-                           long zy, const BnEpi* epi, long tile_first = 0, long tile_count = -1) {
+static int launch_igemm_ws(const WsCall& c, long tile_first = 0, long tile_count = -1) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    const long M = (long)g.N * g.Hout * g.Wout;
+    const long M = geom_rows_out(c.g);
     if (M <= 0) return 0;
-    const int K = g.R * g.S * g.Cin, Np = ws_pad_rows(g.Cout);
-    const BnEpi ep = epi ? *epi : BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
     const size_t lds = (size_t)2 * NP * (BM + BN) * WS_ROW_B + (size_t)8 * BN * sizeof(float);      // two stages + statistics scratch
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)k_igemm_ws<TM, TN, WM, WN, PW, ABL, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    if (NP == 2 && !x_amax) return U2PL_EINVAL;
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    const long yb = ((M - 1) * ldy + g.Cout) * 4;
-    const long wsb1 = (long)(K / 32) * NP * Np * WS_ROW_B;          // one matrix
-    const unsigned* b_amax = (const unsigned*)((const char*)ws + (size_t)batch * wsb1);       // split-fp16: behind the planes
-    // every MATRIX of the batch within 2 GiB (32-bit byte offsets inside a matrix); the batch itself may be larger: the kernel
-    // rebuilds the buffer descriptors per matrix from a 64-bit base (x + z * zx, ws + z * zws, y + z * zy)
-    if (xb >= (1L << 31) || wsb1 >= (1L << 31) || yb >= (1L << 31)) return U2PL_EINVAL;
-    const long resb = ep.res ? ((M - 1) * ep.ldr + g.Cout) * 4 : 0;
-    if (resb >= (1L << 31)) return U2PL_EINVAL;
-    const int mtiles = cdiv(M, BM), ntiles = cdiv(g.Cout, BN);
-    const long all_tiles = (long)mtiles * ntiles * batch;
+    WsExtents e;
+    if (const int rc = ws_extents<NP>(c, e)) return rc;
+    const int mtiles = cdiv(M, BM), ntiles = cdiv(c.g.Cout, BN);
+    const long all_tiles = (long)mtiles * ntiles * c.batch;
     if (all_tiles >= (1L << 30)) return U2PL_EINVAL;
     const long total = tile_count < 0 ? all_tiles : tile_count;      // this launch: tiles [tile_first, tile_first + total)
     if (total <= 0) return 0;
     const unsigned grid = (unsigned)((total < WS_NUM_CUS || !ws_persist()) ? total : WS_NUM_CUS);
 #ifdef U2PL_WS_STAMPS
-    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(d_ws_stamps), &g_ws_stamps, sizeof(void*), 0, hipMemcpyHostToDevice, stream);
+    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(d_ws_stamps), &g_ws_stamps, sizeof(void*), 0, hipMemcpyHostToDevice, c.stream);
 #endif
-    U2PL_LAUNCH((k_igemm_ws<TM, TN, WM, WN, PW, ABL, NP>), dim3(grid), dim3(64 * WM * WN), lds, stream, x, ldx, x_amax,
-                (const unsigned short*)ws, b_amax, bias, y, ldy, g, (unsigned)xb, (unsigned)wsb1, (unsigned)yb, (unsigned)resb, Np, stats, pivot, zx,
-                wsb1 / 2, zy, ep, mtiles, ntiles, (int)total, (int)tile_first);
+    U2PL_LAUNCH((k_igemm_ws<TM, TN, WM, WN, PW, ABL, NP>), dim3(grid), dim3(64 * WM * WN), lds, c.stream, c.x, c.ldx, c.x_amax,
+                (const unsigned short*)c.ws, e.b_amax, c.bias, c.y, c.ldy, c.g, e.xb, e.wsb1, e.yb, e.resb, e.Np, c.stats, c.pivot, c.zx,
+                (long)e.wsb1 / 2, c.zy, c.epi, mtiles, ntiles, (int)total, (int)tile_first);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
 
 template <bool PW, int NP = 3>
-static int launch_igemm_ws_mix(const float* x, long ldx, const float* x_amax, const void* ws, const float* bias, float* y, long ldy,
-                               const ConvGeom& g, hipStream_t stream, float* stats, const float* pivot, int batch, long zx,
-                               long zy, const BnEpi* epi, long wide_tiles, long narrow_tiles) {
-    const long M = (long)g.N * g.Hout * g.Wout;
-    const int K = g.R * g.S * g.Cin, Np = ws_pad_rows(g.Cout);
-    const BnEpi ep = epi ? *epi : BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
+static int launch_igemm_ws_mix(const WsCall& c, long wide_tiles, long narrow_tiles) {
     const size_t lds = (size_t)2 * NP * (128 + 256) * WS_ROW_B + (size_t)8 * 256 * sizeof(float);       // the wide body's
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)k_igemm_ws_mix<PW, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    if (NP == 2 && !x_amax) return U2PL_EINVAL;
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    const long yb = ((M - 1) * ldy + g.Cout) * 4;
-    const long wsb1 = (long)(K / 32) * NP * Np * WS_ROW_B;
-    const unsigned* b_amax = (const unsigned*)((const char*)ws + (size_t)batch * wsb1);
-    if (xb >= (1L << 31) || wsb1 >= (1L << 31) || yb >= (1L << 31)) return U2PL_EINVAL;
-    const long resb = ep.res ? ((M - 1) * ep.ldr + g.Cout) * 4 : 0;
-    if (resb >= (1L << 31)) return U2PL_EINVAL;
-    const int mtiles = cdiv(M, 128), ntw = cdiv(g.Cout, 256);
-    if ((long)mtiles * 2 * ntw * batch >= (1L << 30)) return U2PL_EINVAL;
-    U2PL_LAUNCH((k_igemm_ws_mix<PW, NP>), dim3((unsigned)(WS_NUM_CUS + narrow_tiles)), dim3(512), lds, stream, x, ldx, x_amax,
-                (const unsigned short*)ws, b_amax, bias, y, ldy, g, (unsigned)xb, (unsigned)wsb1, (unsigned)yb, (unsigned)resb, Np, stats, pivot, zx,
-                wsb1 / 2, zy, ep, mtiles, ntw, WS_NUM_CUS, (int)wide_tiles, (int)narrow_tiles);
+    WsExtents e;
+    if (const int rc = ws_extents<NP>(c, e)) return rc;
+    const int mtiles = cdiv(geom_rows_out(c.g), 128), ntw = cdiv(c.g.Cout, 256);
+    if ((long)mtiles * 2 * ntw * c.batch >= (1L << 30)) return U2PL_EINVAL;
+    U2PL_LAUNCH((k_igemm_ws_mix<PW, NP>), dim3((unsigned)(WS_NUM_CUS + narrow_tiles)), dim3(512), lds, c.stream, c.x, c.ldx, c.x_amax,
+                (const unsigned short*)c.ws, e.b_amax, c.bias, c.y, c.ldy, c.g, e.xb, e.wsb1, e.yb, e.resb, e.Np, c.stats, c.pivot, c.zx,
+                (long)e.wsb1 / 2, c.zy, c.epi, mtiles, ntw, WS_NUM_CUS, (int)wide_tiles, (int)narrow_tiles);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
@@ -818,172 +823,169 @@ static int g_ws_abl = 0;
 U2PL_API int u2pl_igemm_ws_set_ablate(int v) { const int old = g_ws_abl; g_ws_abl = v; return old; }
 #endif
 
-// tile choice: 128 x 256 on 8 waves where Cout fills it, 128 x 128 (8 waves of 64 x 32) below; Cout <= 64 is not
-// served here (the callers keep those layers -- 1 % of the network's multiplies -- on k_conv_igemm)
-template <int NP>
-static int run_igemm_ws_np(const float* x, long ldx, const float* x_amax, const void* ws, const float* bias, float* y, long ldy,
-                           const ConvGeom& g, hipStream_t stream, float* stats, const float* pivot, int batch, long zx, long zy,
-                           const BnEpi* epi) {
-    if (g.Cin % BK || !ws) return U2PL_EINVAL;
-    if (epi && (stats || batch != 1 || (g.Cout & 3))) return U2PL_EINVAL;
-    // pointwise: 1x1, stride 1, no padding, forward or data-gradient geometry alike
-    const bool pw = g.R == 1 && g.S == 1 && g.mul == 1 && g.off_h == 0 && g.off_w == 0 && g.log2div == 0 &&
-                    g.Hin == g.Hout && g.Win == g.Wout;
-    auto go = [&](bool narrow, long first, long count) {
-        if (!narrow) return pw ? launch_igemm_ws<2, 2, 2, 4, true, 0, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, first, count)
-                               : launch_igemm_ws<2, 2, 2, 4, false, 0, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, first, count);
-        return pw ? launch_igemm_ws<2, 1, 2, 4, true, 0, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, first, count)
-                  : launch_igemm_ws<2, 1, 2, 4, false, 0, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, first, count);
-    };
-#ifdef U2PL_WS_ABLATE
-    if (g_ws_abl && g.Cout > 128 && pw) {
-#define WS_ABL(A_) case A_: return launch_igemm_ws<2, 2, 2, 4, true, A_, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi)
-        switch (g_ws_abl) { WS_ABL(1); WS_ABL(2); WS_ABL(4); WS_ABL(8); WS_ABL(16); WS_ABL(32); WS_ABL(7); WS_ABL(15); WS_ABL(31); WS_ABL(63); default: return U2PL_EINVAL; }
-#undef WS_ABL
-    }
-#endif
-    // 128 x 256 or 128 x 128 tiles?  One persistent block per CU: a launch costs (tiles of the busiest block) x (time per tile).
-    // Narrow tiles halve the work per tile at ~15 % more time per product (the activation split is amortised over half the
-    // matrix instructions) and fill the last round better: 295 row tiles x 256 columns take 2 rounds of wide tiles but only
-    // 3 rounds of half-size ones (measured 146 -> 125 us for the 1024 -> 256 1x1 convolution at 4 x 97^2).  Third plan,
-    // MIXED: the full rounds as wide tiles and the remainder R <= 128 wide tiles as 2 R narrow ones in a SECOND launch (a
-    // persistent block has one tile shape): 792 tiles of a Winograd batch = 3 rounds + 24 tiles cost 3.6 rounds instead of
-    // 4; a narrow tile (z, mt, 2 nt + h) is half h of the wide tile (z, mt, nt), so the remainder is a contiguous range of
-    // narrow tile numbers.  Both groups run in ONE launch (k_igemm_ws_mix: the narrow blocks are handed to the CUs as the wide
-    // blocks retire); as two launches the plan cost ~15 us more (drain, launch gap, cold prologue: 8 units) and only paid on
-    // long-K layers.  Times in units of one 32-deep chunk of a wide tile; 4 / 2 = fixed cost per tile (prologue, epilogue); fitted to
-    // tools/bench_igemm_ws.py: the mixed plan wins on the long-K launches (2048 -> 256 3x3 at 4 x 97^2: 2194 -> 1953 us,
-    // 2048 -> 512: 410 -> 394 us) and is not chosen for K = 256 .. 1024, where it measured 0-7 % slower.
-    // U2PL_WS_NARROW = 0 (wide only) | 1 (narrow, where Cout <= 256) | 2 (wide / narrow by the model, never mixed) | unset.
-    if (g.Cout <= 128) return go(true, 0, -1);
+// The tile plan.  128 x 256 tiles on 8 waves where Cout fills them, 128 x 128 (8 waves of 64 x 32) below; Cout <= 64 is not served here
+// (the callers keep those layers -- 1 % of the network's multiplies -- on k_conv_igemm).
+// 128 x 256 or 128 x 128 tiles?  One persistent block per CU: a launch costs (tiles of the busiest block) x (time per tile).
+// Narrow tiles halve the work per tile at ~15 % more time per product (the activation split is amortised over half the
+// matrix instructions) and fill the last round better: 295 row tiles x 256 columns take 2 rounds of wide tiles but only
+// 3 rounds of half-size ones (measured 146 -> 125 us for the 1024 -> 256 1x1 convolution at 4 x 97^2).  Third plan,
+// MIXED: the full rounds as wide tiles and the remainder R <= 128 wide tiles as 2 R narrow ones in a SECOND launch (a
+// persistent block has one tile shape): 792 tiles of a Winograd batch = 3 rounds + 24 tiles cost 3.6 rounds instead of
+// 4; a narrow tile (z, mt, 2 nt + h) is half h of the wide tile (z, mt, nt), so the remainder is a contiguous range of
+// narrow tile numbers.  Both groups run in ONE launch (k_igemm_ws_mix: the narrow blocks are handed to the CUs as the wide
+// blocks retire); as two launches the plan cost ~15 us more (drain, launch gap, cold prologue: 8 units) and only paid on
+// long-K layers.  Times in units of one 32-deep chunk of a wide tile; 4 / 2 = fixed cost per tile (prologue, epilogue); fitted to
+// tools/bench_igemm_ws.py: the mixed plan wins on the long-K launches (2048 -> 256 3x3 at 4 x 97^2: 2194 -> 1953 us,
+// 2048 -> 512: 410 -> 394 us) and is not chosen for K = 256 .. 1024, where it measured 0-7 % slower.
+// U2PL_WS_NARROW = 0 (wide only) | 1 (narrow, where Cout <= 256) | 2 (wide / narrow by the model, never mixed) | unset.
+// (Measured and dropped: the 128 x 256 tile on FOUR waves of 128 x 64 -- one wave per SIMD with 512 registers, 18 operand
+// reads per 48 matrix instructions instead of 12 per 24: bit-identical, 5-13 % slower on every wide-tile shape of
+// tools/bench_igemm_ws.py; the second wave of a SIMD does cover stalls of the first.)
+enum WsPlanKind { WS_WIDE = 0, WS_NARROW = 1, WS_MIXED = 2, WS_MIXED2 = 3 };      // MIXED2: the mixed plan as two launches
+// wide: 128 x 256 tiles (the full rounds of a mixed plan), narrow: 128 x 128 tiles (the remainder of a mixed plan)
+struct WsPlan { WsPlanKind kind; long wide, narrow; };
+static WsPlan plan_igemm_ws(long M, long K, int Cout, int batch, int np) {
+    const long mt = cdiv(M, 128), nkc = K / BK;
+    const long ntw = cdiv(Cout, 256), ntn = cdiv(Cout, 128);
+    const long tw = mt * ntw * batch, tn = mt * ntn * batch;
+    const WsPlan wide = {WS_WIDE, tw, 0}, narrow = {WS_NARROW, 0, tn};
+    if (Cout <= 128) return narrow;
     static int force = -2;
     if (force == -2) { const char* e = getenv("U2PL_WS_NARROW"); force = (e && *e) ? atoi(e) : -1; }
-    const long M_ = (long)g.N * g.Hout * g.Wout;
-    const long mt = cdiv(M_, 128), nkc = (long)(g.R * g.S * g.Cin) / BK;
-    const long ntw = cdiv(g.Cout, 256), ntn = cdiv(g.Cout, 128);
-    const long tw = mt * ntw * batch, tn = mt * ntn * batch;
     // (split-fp16: a chunk takes half the time, the fixed cost per tile -- prologue, stores -- does not)
-    const double fix = NP == 3 ? 1.0 : ws_fix2();
+    const double fix = np == 3 ? 1.0 : ws_fix2();
     const double cw1 = nkc + 4.0 * fix, cn1 = 0.5 * 1.15 * nkc + 2.0 * fix;
     const double cw = (double)cdiv(tw, WS_NUM_CUS) * cw1, cn = (double)cdiv(tn, WS_NUM_CUS) * cn1;
-    if (force == 0) return go(false, 0, -1);
-    if (force == 1) return go(g.Cout <= 256, 0, -1);
+    if (force == 0) return wide;
+    if (force == 1) return Cout <= 256 ? narrow : wide;
     const long full = tw / WS_NUM_CUS * WS_NUM_CUS, rem = tw - full;
     const bool can_mix = force != 2 && ws_persist() && ntn == 2 * ntw && full > 0 && rem > 0 && 2 * rem <= WS_NUM_CUS;
     static int two_launch = -1;      // U2PL_WS_MIX2=1: the mixed plan as two launches (A/B of the one-launch form)
     if (two_launch < 0) { const char* e = getenv("U2PL_WS_MIX2"); two_launch = (e && *e) ? (atoi(e) != 0) : 0; }
     const double cm = can_mix ? (double)(full / WS_NUM_CUS) * cw1 + cn1 + (two_launch ? 8.0 : 2.0) * fix : 1e30;
-    if (cm < 0.97 * cw && cm < cn) {
-        if (!two_launch)
-            return pw ? launch_igemm_ws_mix<true, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, full, 2 * rem)
-                      : launch_igemm_ws_mix<false, NP>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi, full, 2 * rem);
-        const int rc = go(false, 0, full);
-        return rc ? rc : go(true, 2 * full, 2 * rem);
-    }
-    return go(cn < 0.97 * cw, 0, -1);
-    // (Measured and dropped: the 128 x 256 tile on FOUR waves of 128 x 64 -- one wave per SIMD with 512 registers, 18 operand
-    // reads per 48 matrix instructions instead of 12 per 24: bit-identical, 5-13 % slower on every wide-tile shape of
-    // tools/bench_igemm_ws.py; the second wave of a SIMD does cover stalls of the first.)
+    if (cm < 0.97 * cw && cm < cn) return WsPlan{two_launch ? WS_MIXED2 : WS_MIXED, full, 2 * rem};
+    return cn < 0.97 * cw ? narrow : wide;
+}
+U2PL_API int u2pl_igemm_ws_plan(long M, int K, int Cout, int batch, int np, int* out) {
+    if (M <= 0 || K <= 0 || Cout <= 0 || batch <= 0 || (np != 2 && np != 3) || !out) return U2PL_EINVAL;
+    const WsPlan p = plan_igemm_ws(M, K, Cout, batch, np);
+    if (M >= (1L << 31) || p.wide >= (1L << 30) || p.narrow >= (1L << 30)) return U2PL_EINVAL;      // (as the launches do)
+    out[0] = (int)p.kind; out[1] = (int)p.wide; out[2] = (int)p.narrow;
+    return 0;
 }
 
-// x_amax == NULL: the bf16 three-piece planes of u2pl_weight_split3_f32 (six products); x_amax != NULL: split-fp16 -- the planes
-// of u2pl_weight_split2h_f32 and the device scalar max |x| of the activation operand (three products)
-static int run_igemm_ws(const float* x, long ldx, const void* ws, const float* bias, float* y, long ldy, const ConvGeom& g,
-                        hipStream_t stream, float* stats = nullptr, const float* pivot = nullptr, int batch = 1,
-                        long zx = 0, long zy = 0, const BnEpi* epi = nullptr, const float* x_amax = nullptr) {
-    return x_amax ? run_igemm_ws_np<2>(x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi)
-                  : run_igemm_ws_np<3>(x, ldx, nullptr, ws, bias, y, ldy, g, stream, stats, pivot, batch, zx, zy, epi);
+template <int NP>
+static int run_igemm_ws_np(const WsCall& c) {
+    const ConvGeom& g = c.g;
+    if (!geom_ok(g) || g.Cin % BK || !c.ws) return U2PL_EINVAL;
+    if (c.epi.mean && (c.stats || c.batch != 1 || (g.Cout & 3))) return U2PL_EINVAL;
+    // pointwise: 1x1, stride 1, no padding, forward or data-gradient geometry alike
+    const bool pw = g.R == 1 && g.S == 1 && g.mul == 1 && g.off_h == 0 && g.off_w == 0 && g.log2div == 0 &&
+                    g.Hin == g.Hout && g.Win == g.Wout;
+    auto go = [&](bool narrow, long first, long count) {
+        if (!narrow) return pw ? launch_igemm_ws<2, 2, 2, 4, true, 0, NP>(c, first, count) : launch_igemm_ws<2, 2, 2, 4, false, 0, NP>(c, first, count);
+        return pw ? launch_igemm_ws<2, 1, 2, 4, true, 0, NP>(c, first, count) : launch_igemm_ws<2, 1, 2, 4, false, 0, NP>(c, first, count);
+    };
+#ifdef U2PL_WS_ABLATE
+    if (g_ws_abl && g.Cout > 128 && pw) {
+#define WS_ABL(A_) case A_: return launch_igemm_ws<2, 2, 2, 4, true, A_, NP>(c)
+        switch (g_ws_abl) { WS_ABL(1); WS_ABL(2); WS_ABL(4); WS_ABL(8); WS_ABL(16); WS_ABL(32); WS_ABL(7); WS_ABL(15); WS_ABL(31); WS_ABL(63); default: return U2PL_EINVAL; }
+#undef WS_ABL
+    }
+#endif
+    const WsPlan p = plan_igemm_ws(geom_rows_out(g), (long)g.R * g.S * g.Cin, g.Cout, c.batch, NP);
+    switch (p.kind) {
+        case WS_WIDE: return go(false, 0, -1);
+        case WS_NARROW: return go(true, 0, -1);
+        case WS_MIXED: return pw ? launch_igemm_ws_mix<true, NP>(c, p.wide, p.narrow) : launch_igemm_ws_mix<false, NP>(c, p.wide, p.narrow);
+        default: break;
+    }
+    const int rc = go(false, 0, p.wide);
+    return rc ? rc : go(true, 2 * p.wide, p.narrow);
 }
+static int run_igemm_ws(const WsCall& c) { return c.x_amax ? run_igemm_ws_np<2>(c) : run_igemm_ws_np<3>(c); }
 
 // ---- entry points: the conv.hip calls with the weight operand given as split planes (u2pl_weight_split3_f32 of the
-//      [Cout][R*S*Cin] matrix for the forward, of the transposed [Cin][R*S*Cout] matrix for the data gradient)
+//      [Cout][R*S*Cin] matrix for the forward, of the transposed [Cin][R*S*Cout] matrix for the data gradient).  The *_wsh_* (split-fp16,
+//      round 6) forms are the same calls with the planes of u2pl_weight_split2h_f32 and x_amax = the device scalar max |x| of the
+//      activation operand (u2pl_absmax_f32, or a producer's fused maximum; any upper bound within 2^8 of the true maximum keeps
+//      fp32-class accuracy, a bound BELOW the maximum overflows fp16).  A pair differs in that pointer alone, which a *_wsh_* entry refuses as NULL.
 U2PL_API int u2pl_igemm_ws_stat_blocks(int N, int Hout, int Wout) { return cdiv((long)N * Hout * Wout, 128); }
 
-U2PL_API int u2pl_conv2d_fwd_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y, long ldy,
-                                    int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S,
-                                    int stride, int pad, int dil, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream);
+static WsCall ws_call(const float* x, long ldx, const float* x_amax, const void* ws, const float* bias, float* y, long ldy, const ConvGeom& g,
+                      hipStream_t stream, float* stats = nullptr, const float* pivot = nullptr) {
+    return WsCall{x, ldx, x_amax, ws, bias, y, ldy, g, stream, stats, pivot, 1, 0, 0, BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr}};
 }
-U2PL_API int u2pl_conv2d_fwd_bnstats_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y,
-                                            long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
-                                            int R, int S, int stride, int pad, int dil, const float* pivot,
-                                            float* stats_partial, hipStream_t stream) {
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream, stats_partial, pivot);
-}
-U2PL_API int u2pl_conv2d_fwd_bnact_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y,
-                                          long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
-                                          int S, int stride, int pad, int dil, const float* mean, const float* invstd,
-                                          const float* gamma, const float* beta, const float* res, long ldr, int relu,
-                                          hipStream_t stream) {
-    if (!mean || !invstd || !gamma || !beta || (Cout & 3) || (res && (ldr & 3))) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    const BnEpi epi = {mean, invstd, gamma, beta, res, ldr, relu, nullptr};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream, nullptr, nullptr, 1, 0, 0, &epi);
-}
-U2PL_API int u2pl_conv2d_dgrad_ws_f32(const float* dy, long lddy, const void* wTsplit, float* dx, long lddx, int N, int Hin,
-                                      int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad,
-                                      int dil, hipStream_t stream) {
-    int l2 = 0;
-    while ((1 << l2) < stride) ++l2;
-    if ((1 << l2) != stride) return U2PL_EINVAL;
-    ConvGeom g = {N, Hout, Wout, Cout, Hin, Win, Cin, R, S, 1, pad, pad, -dil, l2};
-    return run_igemm_ws(dy, lddy, wTsplit, nullptr, dx, lddx, g, stream);
+// forward with the eval-BatchNorm epilogue; y_amax: split-fp16 only (the output's fused maximum)
+static int ws_bnact(WsCall c, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* res, long ldr,
+                    int relu, float* y_amax) {
+    if (!mean || !invstd || !gamma || !beta || (c.g.Cout & 3) || (res && (ldr & 3))) return U2PL_EINVAL;
+    c.epi = BnEpi{mean, invstd, gamma, beta, res, ldr, relu, (unsigned*)y_amax};
+    return run_igemm_ws(c);
 }
 // batch of row-major GEMMs Y_z[M][Nn] = X_z[M][K] * W_z[Nn][K]^T with W_z given as split planes (batch = the matrices
 // of ONE u2pl_weight_split3_f32 call): the Winograd component products
-U2PL_API int u2pl_gemm_batched_ws_f32(const float* x, long ldx, long zx, const void* wsplit, float* y, long ldy, long zy,
-                                      long M, int K, int Nn, int batch, hipStream_t stream) {
+static int ws_gemm_batched(WsCall c, long M, int batch, long zx, long zy) {
     if (M <= 0 || batch <= 0) return 0;
     if (M >= (1L << 31)) return U2PL_EINVAL;
-    ConvGeom g = {1, (int)M, 1, K, (int)M, 1, Nn, 1, 1, 1, 0, 0, 1, 0};
-    return run_igemm_ws(x, ldx, wsplit, nullptr, y, ldy, g, stream, nullptr, nullptr, batch, zx, zy);
+    c.batch = batch; c.zx = zx; c.zy = zy;
+    return run_igemm_ws(c);
 }
 
-// ---- split-fp16 entry points (round 6): the same calls with the planes of u2pl_weight_split2h_f32 and x_amax = the device scalar
-//      max |x| of the activation operand (u2pl_absmax_f32, or a producer's fused maximum; any upper bound within 2^8 of the true
-//      maximum keeps fp32-class accuracy, a bound BELOW the maximum overflows fp16)
-U2PL_API int u2pl_conv2d_fwd_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y, long ldy,
-                                     int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S,
-                                     int stride, int pad, int dil, hipStream_t stream) {
+U2PL_API int u2pl_conv2d_fwd_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y, long ldy, int N, int Hin, int Win,
+                                    int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil, hipStream_t stream) {
+    return run_igemm_ws(ws_call(x, ldx, nullptr, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
+}
+U2PL_API int u2pl_conv2d_fwd_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y, long ldy, int N,
+                                     int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                                     hipStream_t stream) {
     if (!x_amax) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream, nullptr, nullptr, 1, 0, 0, nullptr, x_amax);
+    return run_igemm_ws(ws_call(x, ldx, x_amax, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
 }
-U2PL_API int u2pl_conv2d_fwd_bnstats_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y,
-                                             long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
-                                             int R, int S, int stride, int pad, int dil, const float* pivot,
-                                             float* stats_partial, hipStream_t stream) {
+U2PL_API int u2pl_conv2d_fwd_bnstats_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y, long ldy, int N, int Hin,
+                                            int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                                            const float* pivot, float* stats_partial, hipStream_t stream) {
+    return run_igemm_ws(ws_call(x, ldx, nullptr, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream,
+                                stats_partial, pivot));
+}
+U2PL_API int u2pl_conv2d_fwd_bnstats_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y, long ldy,
+                                             int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad,
+                                             int dil, const float* pivot, float* stats_partial, hipStream_t stream) {
     if (!x_amax) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream, stats_partial, pivot, 1, 0, 0, nullptr, x_amax);
+    return run_igemm_ws(ws_call(x, ldx, x_amax, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream,
+                                 stats_partial, pivot));
 }
-U2PL_API int u2pl_conv2d_fwd_bnact_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y,
-                                           long ldy, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R,
-                                           int S, int stride, int pad, int dil, const float* mean, const float* invstd,
-                                           const float* gamma, const float* beta, const float* res, long ldr, int relu,
-                                           float* y_amax, hipStream_t stream) {
-    if (!x_amax || !mean || !invstd || !gamma || !beta || (Cout & 3) || (res && (ldr & 3))) return U2PL_EINVAL;
-    ConvGeom g = {N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, -pad, -pad, dil, 0};
-    const BnEpi epi = {mean, invstd, gamma, beta, res, ldr, relu, (unsigned*)y_amax};
-    return run_igemm_ws(x, ldx, wsplit, bias, y, ldy, g, stream, nullptr, nullptr, 1, 0, 0, &epi, x_amax);
+U2PL_API int u2pl_conv2d_fwd_bnact_ws_f32(const float* x, long ldx, const void* wsplit, const float* bias, float* y, long ldy, int N, int Hin,
+                                          int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                                          const float* mean, const float* invstd, const float* gamma, const float* beta, const float* res, long ldr,
+                                          int relu, hipStream_t stream) {
+    return ws_bnact(ws_call(x, ldx, nullptr, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream), mean,
+                    invstd, gamma, beta, res, ldr, relu, nullptr);
 }
-U2PL_API int u2pl_conv2d_dgrad_wsh_f32(const float* dy, long lddy, const float* dy_amax, const void* wTsplit, float* dx, long lddx, int N,
-                                       int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad,
-                                       int dil, hipStream_t stream) {
+U2PL_API int u2pl_conv2d_fwd_bnact_wsh_f32(const float* x, long ldx, const float* x_amax, const void* wsplit, const float* bias, float* y, long ldy,
+                                           int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                                           const float* mean, const float* invstd, const float* gamma, const float* beta, const float* res, long ldr,
+                                           int relu, float* y_amax, hipStream_t stream) {
+    if (!x_amax) return U2PL_EINVAL;
+    return ws_bnact(ws_call(x, ldx, x_amax, wsplit, bias, y, ldy, geom_fwd(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream), mean,
+                    invstd, gamma, beta, res, ldr, relu, y_amax);
+}
+U2PL_API int u2pl_conv2d_dgrad_ws_f32(const float* dy, long lddy, const void* wTsplit, float* dx, long lddx, int N, int Hin, int Win, int Cin,
+                                      int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil, hipStream_t stream) {
+    return run_igemm_ws(ws_call(dy, lddy, nullptr, wTsplit, nullptr, dx, lddx, geom_dgrad(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
+}
+U2PL_API int u2pl_conv2d_dgrad_wsh_f32(const float* dy, long lddy, const float* dy_amax, const void* wTsplit, float* dx, long lddx, int N, int Hin,
+                                       int Win, int Cin, int Hout, int Wout, int Cout, int R, int S, int stride, int pad, int dil,
+                                       hipStream_t stream) {
     if (!dy_amax) return U2PL_EINVAL;
-    int l2 = 0;
-    while ((1 << l2) < stride) ++l2;
-    if ((1 << l2) != stride) return U2PL_EINVAL;
-    ConvGeom g = {N, Hout, Wout, Cout, Hin, Win, Cin, R, S, 1, pad, pad, -dil, l2};
-    return run_igemm_ws(dy, lddy, wTsplit, nullptr, dx, lddx, g, stream, nullptr, nullptr, 1, 0, 0, nullptr, dy_amax);
+    return run_igemm_ws(ws_call(dy, lddy, dy_amax, wTsplit, nullptr, dx, lddx, geom_dgrad(N, Hin, Win, Cin, Hout, Wout, Cout, R, S, stride, pad, dil), stream));
 }
-U2PL_API int u2pl_gemm_batched_wsh_f32(const float* x, long ldx, long zx, const float* x_amax, const void* wsplit, float* y, long ldy,
-                                       long zy, long M, int K, int Nn, int batch, hipStream_t stream) {
+U2PL_API int u2pl_gemm_batched_ws_f32(const float* x, long ldx, long zx, const void* wsplit, float* y, long ldy, long zy, long M, int K, int Nn,
+                                      int batch, hipStream_t stream) {
+    return ws_gemm_batched(ws_call(x, ldx, nullptr, wsplit, nullptr, y, ldy, geom_gemm(M, K, Nn), stream), M, batch, zx, zy);
+}
+U2PL_API int u2pl_gemm_batched_wsh_f32(const float* x, long ldx, long zx, const float* x_amax, const void* wsplit, float* y, long ldy, long zy,
+                                       long M, int K, int Nn, int batch, hipStream_t stream) {
     if (!x_amax) return U2PL_EINVAL;
-    if (M <= 0 || batch <= 0) return 0;
-    if (M >= (1L << 31)) return U2PL_EINVAL;
-    ConvGeom g = {1, (int)M, 1, K, (int)M, 1, Nn, 1, 1, 1, 0, 0, 1, 0};
-    return run_igemm_ws(x, ldx, wsplit, nullptr, y, ldy, g, stream, nullptr, nullptr, batch, zx, zy, nullptr, x_amax);
+    return ws_gemm_batched(ws_call(x, ldx, x_amax, wsplit, nullptr, y, ldy, geom_gemm(M, K, Nn), stream), M, batch, zx, zy);
 }

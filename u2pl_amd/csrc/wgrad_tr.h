@@ -2,9 +2,21 @@
 #pragma once
 #include "conv_geom.h"
 
+// one weight-gradient call (every kernel family of conv.hip and wgrad_tr.hip): dY and X rows, the slabs, the geometry (taps = R * S; a
+// batched call passes its components as taps, zdy / zx floats apart), the stream and, for split-fp16 (three products), the device-scalar
+// maxima of the two operands (both NULL: six bf16 piece products)
+struct WgradCall {
+    const float* dy; long lddy; const float* x; long ldx; float* part; ConvGeom g; hipStream_t stream; long zdy, zx;
+    const float *dy_amax, *x_amax;
+};
+// slabs of the pixel range: ctiles = Cin tiles, nsplit slabs of cps 32-pixel chunks each
+struct WgradSlabs { int ctiles, nsplit, cps; };
+
+// both operand extents of a weight-gradient launch; false: one of them reaches 2 GiB
+static inline bool wgrad_extents(const WgradCall& c, unsigned& dyb, unsigned& xb) {
+    return span_bytes(geom_rows_out(c.g), c.lddy, c.g.Cout, dyb) && span_bytes(geom_rows_in(c.g), c.ldx, c.g.Cin, xb);
+}
+
 bool wgrad_tr_eligible(const ConvGeom& g);
-// slabs of the pixel range: ctiles = Cin tiles, nsplit slabs of cps 32-pixel chunks each; taps = R * S (or the batch)
-void wgrad_tr_plan(const ConvGeom& g, int taps, int& ctiles, int& nsplit, int& cps);
-// dy_amax / x_amax: NULL (six bf16 piece products) or the device-scalar maxima of the two operands (split-fp16, three products)
-int launch_wgrad_tr(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g, int ctiles, int nsplit,
-                    int cps, hipStream_t stream, long zdy, long zx, const float* dy_amax = nullptr, const float* x_amax = nullptr);
+WgradSlabs wgrad_tr_plan(const ConvGeom& g);
+int launch_wgrad_tr(const WgradCall& c, const WgradSlabs& s);

@@ -306,11 +306,10 @@ static int wt_bn(const ConvGeom& g) {
     return g.Cin > 128 ? 256 : 128;
 }
 // slabs: one block per CU and round; the plan minimises (rounds of 256 blocks) x (chunks per slab + fixed cost per block)
-void wgrad_tr_plan(const ConvGeom& g, int taps, int& ctiles, int& nsplit, int& cps) {
-    const long M = (long)g.N * g.Hout * g.Wout;
-    const long nchunks = (M + BK - 1) / BK;
-    ctiles = cdiv(g.Cin, wt_bn(g));
-    const long tiles = (long)cdiv(g.Cout, 128) * ctiles * taps;
+WgradSlabs wgrad_tr_plan(const ConvGeom& g) {
+    const long nchunks = (geom_rows_out(g) + BK - 1) / BK;
+    const int ctiles = cdiv(g.Cin, wt_bn(g));
+    const long tiles = (long)cdiv(g.Cout, 128) * ctiles * g.R * g.S;
     long best = 1;
     double bestc = 1e30;
     const long maxs = nchunks / 6 > 0 ? nchunks / 6 : 1;
@@ -321,13 +320,12 @@ void wgrad_tr_plan(const ConvGeom& g, int taps, int& ctiles, int& nsplit, int& c
         const double cost = rounds * (c + 5.0) + 0.15 * s;             // 5: prologue + slab write; 0.15 / slab: its share of the reduce
         if (cost < bestc) { bestc = cost; best = s; }
     }
-    cps = (int)((nchunks + best - 1) / best);
-    nsplit = (int)((nchunks + cps - 1) / cps);
+    const int cps = (int)((nchunks + best - 1) / best);
+    return WgradSlabs{ctiles, (int)((nchunks + cps - 1) / cps), cps};
 }
 
 template <int TN, bool PW, int NP>
-static int launch1(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g, int ctiles, int nsplit,
-                   int cps, int taps, hipStream_t stream, long zdy, long zx, const float* dy_amax, const float* x_amax) {
+static int launch1(const WgradCall& c, const WgradSlabs& s) {
     constexpr int CH = 128 + 128 * TN, PITCH = CH * 2 + 64;
     const size_t lds = (size_t)2 * NP * BK * PITCH;
     static bool attr_set = false;
@@ -335,31 +333,24 @@ static int launch1(const float* dy, long lddy, const float* x, long ldx, float* 
         (void)hipFuncSetAttribute((const void*)k_wgrad_tr<TN, PW, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    const long dyb = (((long)g.N * g.Hout * g.Wout - 1) * lddy + g.Cout) * 4;
-    const long xb = (((long)g.N * g.Hin * g.Win - 1) * ldx + g.Cin) * 4;
-    if (dyb >= (1L << 31) || xb >= (1L << 31)) return U2PL_EINVAL;
-    dim3 grid((unsigned)(ctiles * taps), (unsigned)cdiv(g.Cout, 128), (unsigned)nsplit);
-    U2PL_LAUNCH((k_wgrad_tr<TN, PW, NP>), grid, dim3(512), lds, stream, dy, lddy, x, ldx, part, g, ctiles, cps, (unsigned)dyb,
-                (unsigned)xb, zdy, zx, dy_amax, x_amax);
+    unsigned dyb, xb;
+    if (!wgrad_extents(c, dyb, xb)) return U2PL_EINVAL;
+    dim3 grid((unsigned)(s.ctiles * c.g.R * c.g.S), (unsigned)cdiv(c.g.Cout, 128), (unsigned)s.nsplit);
+    U2PL_LAUNCH((k_wgrad_tr<TN, PW, NP>), grid, dim3(512), lds, c.stream, c.dy, c.lddy, c.x, c.ldx, c.part, c.g, s.ctiles, s.cps, dyb, xb,
+                c.zdy, c.zx, c.dy_amax, c.x_amax);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
 template <int NP>
-static int launch_np(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g, int ctiles, int nsplit,
-                     int cps, hipStream_t stream, long zdy, long zx, const float* dy_amax, const float* x_amax) {
-    const int taps = g.R * g.S;
+static int launch_np(const WgradCall& c, const WgradSlabs& s) {
+    const ConvGeom& g = c.g;
     // pointwise: identity gather (1x1 stride 1 without padding; the Winograd component batches pass step = 0, offsets 0)
-    const bool pw = g.mul == 1 && g.off_h == 0 && g.off_w == 0 && g.Hin == g.Hout && g.Win == g.Wout && (g.step == 0 || taps == 1);
-    if (wt_bn(g) == 256)
-        return pw ? launch1<2, true, NP>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, taps, stream, zdy, zx, dy_amax, x_amax)
-                  : launch1<2, false, NP>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, taps, stream, zdy, zx, dy_amax, x_amax);
-    return pw ? launch1<1, true, NP>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, taps, stream, zdy, zx, dy_amax, x_amax)
-              : launch1<1, false, NP>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, taps, stream, zdy, zx, dy_amax, x_amax);
+    const bool pw = g.mul == 1 && g.off_h == 0 && g.off_w == 0 && g.Hin == g.Hout && g.Win == g.Wout && (g.step == 0 || g.R * g.S == 1);
+    if (wt_bn(g) == 256) return pw ? launch1<2, true, NP>(c, s) : launch1<2, false, NP>(c, s);
+    return pw ? launch1<1, true, NP>(c, s) : launch1<1, false, NP>(c, s);
 }
 // dy_amax / x_amax both NULL: the six-product bf16 form; both given: split-fp16 (three products)
-int launch_wgrad_tr(const float* dy, long lddy, const float* x, long ldx, float* part, const ConvGeom& g, int ctiles, int nsplit,
-                    int cps, hipStream_t stream, long zdy, long zx, const float* dy_amax, const float* x_amax) {
-    if ((dy_amax == nullptr) != (x_amax == nullptr)) return U2PL_EINVAL;
-    return dy_amax ? launch_np<2>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, stream, zdy, zx, dy_amax, x_amax)
-                   : launch_np<3>(dy, lddy, x, ldx, part, g, ctiles, nsplit, cps, stream, zdy, zx, nullptr, nullptr);
+int launch_wgrad_tr(const WgradCall& c, const WgradSlabs& s) {
+    if ((c.dy_amax == nullptr) != (c.x_amax == nullptr)) return U2PL_EINVAL;
+    return c.dy_amax ? launch_np<2>(c, s) : launch_np<3>(c, s);
 }
