@@ -568,6 +568,23 @@ int u2pl_maxpool3s2_fwd_f32(const float* x, long ldx, int N, int H, int W, int C
                             unsigned char* tap, hipStream_t stream);
 int u2pl_maxpool3s2_bwd_f32(const float* dy, long lddy, const unsigned char* tap, int N, int H, int W, int C, int Ho,
                             int Wo, float* dx, long lddx, hipStream_t stream);
+/* Pyramid pooling (csrc/pool.hip): nn.AdaptiveAvgPool2d((b, b)) of x [N*H*W][C] (pitch ldx) for up to four levels b0..b3
+   (each >= 1; 0 = level unused, its pointer ignored), all levels in one launch; level l writes y_l [N*b*b][C] (pitch ldy_l).
+   Window rule (torch's), per axis: window i of b over H is [floor(i*H/b), ceil((i+1)*H/b)); neighbouring windows share a row
+   when H % b != 0; b may exceed H.  The mean divides the fp32 sum by the true window area.  C % 4 == 0, pitches multiples of
+   4 and >= C, bases 16-byte aligned, levels <= 16384, H and W <= 65535, N*H*W < 2^31; 1001 before any launch for C % 4, a
+   level < 0, all levels 0, a null x or a null y of a used level.  Fixed summation order (first comment block of csrc/pool.hip): the same bits on every run. */
+int u2pl_pyramid_pool_fwd_f32(const float* x, long ldx, int N, int H, int W, int C, int b0, int b1, int b2, int b3,
+                              float* y0, long ldy0, float* y1, long ldy1, float* y2, long ldy2, float* y3, long ldy3,
+                              hipStream_t stream);
+/* its backward, a gather: dx[p] = sum over levels (in argument order; a null g_l is skipped) of sum over the windows (i, j)
+   that contain pixel p, ascending, of g_l[window] * (1.0f / area(window)), then + add[p] when add is not null (the gradient x
+   receives from its other consumer, pitch ldadd).  The windows of a level that contain row h are the range
+   floor(h*b/H) .. ceil((h+1)*b/H) - 1.  dx [N*H*W][C] (pitch lddx) is written exactly once; no atomics, no memset.
+   1001 before any launch for C % 4, a level < 0, all levels 0 or a null dx. */
+int u2pl_pyramid_pool_bwd_f32(const float* g0, long ldg0, const float* g1, long ldg1, const float* g2, long ldg2,
+                              const float* g3, long ldg3, const float* add, long ldadd, int N, int H, int W, int C,
+                              int b0, int b1, int b2, int b3, float* dx, long lddx, hipStream_t stream);
 /* torch.cat / slices (base.py:99, decoder.py:117), 1x1 -> HxW bilinear broadcast (base.py:92-94) */
 int u2pl_copy_rows_f32(const float* src, long lds, float* dst, long ldd, long M, int C, int accumulate,
                        hipStream_t stream);

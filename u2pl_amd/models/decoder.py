@@ -1,5 +1,5 @@
 """DeepLabv3 / DeepLabv3+ decoders and the auxiliary head (reference:
-u2pl/models/decoder.py).  nn.Sequential containers keep the reference's
+u2pl/models/decoder.py), and a pyramid-pooling decoder (dec_pspnet).  nn.Sequential containers keep the reference's
 indices (``classifier.8.weight``); ReLU / Dropout2d entries are markers fused
 into the BatchNorm apply kernel by u2pl_amd.nn.run_seq."""
 import torch.nn as nn
@@ -67,6 +67,56 @@ class dec_deeplabv3_plus(nn.Module):
         res = {"pred": K.run_seq(self.classifier, aspp_out)}
         if self.rep_head and need_rep:
             res["rep"] = K.run_seq(self.representation, aspp_out)
+        return res
+
+
+class dec_pspnet(nn.Module):
+    """Pyramid-pooling head (PSPNet, Zhao et al. 2017, section 3.2; no reference line: the reference has the two ASPP heads only).
+    ppm.{i}: AdaptiveAvgPool2d(bins[i]) -> 1x1 (in_planes / len(bins), no bias) -> norm -> ReLU, up-sampled to the input's size
+    (bilinear, align_corners=True) and concatenated behind the input; head: dense 3x3 from 2 in_planes to inner_planes -> norm
+    -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: a `representation` tower (3x3 to 256 -> norm -> ReLU ->
+    Dropout2d(0.1) -> 1x1 to 256) beside the classifier, on the head's output, for the contrastive loss.
+    All levels are pooled by one launch and the input's gradient is written by one gather (K.pyramid_pool)."""
+
+    def __init__(self, in_planes, num_classes=19, inner_planes=512, sync_bn=False, bins=(1, 2, 3, 6), rep_head=False):
+        super().__init__()
+        bins = K.check_pyramid_bins(bins)
+        if in_planes % (4 * len(bins)):
+            raise ValueError("dec_pspnet: in_planes (%d) must be a multiple of 4 * len(bins) = %d (float4 rows in every "
+                             "branch)" % (in_planes, 4 * len(bins)))
+        norm_layer = norm_layer_for(sync_bn)
+        self.bins = bins
+        self.rep_head = rep_head
+        red = in_planes // len(bins)
+        self.ppm = nn.ModuleList(
+            nn.Sequential(
+                nn.AdaptiveAvgPool2d(b),  # marker: executed by K.pyramid_pool
+                K.Conv2d(in_planes, red, kernel_size=1, bias=False),
+                norm_layer(red),
+                nn.ReLU(inplace=True),
+            ) for b in bins)
+        self.head = nn.Sequential(
+            K.Conv2d(2 * in_planes, inner_planes, kernel_size=3, stride=1, padding=1, dilation=1, bias=False),
+            norm_layer(inner_planes), nn.ReLU(inplace=True), nn.Dropout2d(0.1))
+        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        if rep_head:
+            self.representation = nn.Sequential(
+                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
+                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
+                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+
+    def forward(self, x, need_rep=True):
+        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
+            x = x[-1]
+        h, w = x.size()[-2:]
+        x_pass, *pooled = K.pyramid_pool(x, self.bins)
+        # independent conv -> BN -> ReLU units: under a process group their statistics share one packed exchange
+        f = K.conv_bn_group([(m[1], m[2], p, True, None) for m, p in zip(self.ppm, pooled)])
+        feat = K.cat_channels((x_pass, *(K.upsample_bilinear(t, (h, w)) for t in f)))
+        feat = K.run_seq(self.head, feat)
+        res = {"pred": self.classifier(feat)}
+        if self.rep_head and need_rep:
+            res["rep"] = K.run_seq(self.representation, feat)
         return res
 
 

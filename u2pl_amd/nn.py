@@ -1355,6 +1355,65 @@ def global_avg_pool(x):
     return _GapFn.apply(x)
 
 
+PSP_MAX_LEVELS = 4
+
+
+def check_pyramid_bins(bins):
+    """the level grids u2pl_pyramid_pool_* take: one to four square levels, each >= 1"""
+    bins = tuple(int(b) for b in bins)
+    if not 1 <= len(bins) <= PSP_MAX_LEVELS:
+        raise ValueError("pyramid pooling takes one to %d levels, got %d" % (PSP_MAX_LEVELS, len(bins)))
+    if min(bins) < 1:
+        raise ValueError("pyramid pooling levels are >= 1, got %r" % (bins,))
+    return bins
+
+
+class _PyramidPoolFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d((b, b)) for every b of `bins` in one launch (csrc/pool.hip), plus x itself handed through: the
+    gradient of that pass-through output (the concat's slice) reaches backward() together with the pooled gradients and goes
+    into the gather kernel as its `add` operand, so dx is written once and autograd adds nothing over the wide tensor."""
+
+    @staticmethod
+    def forward(ctx, x, bins):
+        xr, ldx = as_rows(x)
+        N, C, H, W = xr.shape
+        lv = list(bins) + [0] * (PSP_MAX_LEVELS - len(bins))
+        ys = [new_act(N, C, b, b, xr.device) for b in bins]
+        args = []
+        for k in range(PSP_MAX_LEVELS):
+            args += [ys[k] if k < len(bins) else None, C]
+        call("u2pl_pyramid_pool_fwd_f32", xr, ldx, N, H, W, C, *lv, *args)
+        ctx.meta = (N, C, H, W, lv)
+        ctx.set_materialize_grads(False)
+        return (x, *ys)     # (an input returned as it is becomes an output of this node that aliases it)
+
+    @staticmethod
+    def backward(ctx, g_pass, *gs):
+        N, C, H, W, lv = ctx.meta
+        args, dev = [], None
+        for k in range(PSP_MAX_LEVELS):
+            g = gs[k] if k < len(gs) else None
+            ld = C
+            if g is not None:
+                g, ld = as_rows(g)
+                dev = g.device
+            args += [g, ld]
+        add, ldadd = (None, C) if g_pass is None else as_rows(g_pass)
+        if dev is None:
+            if add is None:
+                return None, None
+            dev = add.device
+        dx = new_act(N, C, H, W, dev)
+        call("u2pl_pyramid_pool_bwd_f32", *args, add, ldadd, N, H, W, C, *lv, dx, C)
+        return dx, None
+
+
+def pyramid_pool(x, bins):
+    """-> (x_pass, p_0, ..., p_k): p_i = F.adaptive_avg_pool2d(x, bins[i]); x_pass is x through the same autograd node (give IT,
+    not x, to x's other consumer -- see _PyramidPoolFn)."""
+    return _PyramidPoolFn.apply(x, check_pyramid_bins(bins))
+
+
 class _BroadcastFn(torch.autograd.Function):
     """bilinear(align_corners=True) up-sampling of a 1x1 map == broadcast (base.py:92-94)."""
 
