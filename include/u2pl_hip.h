@@ -585,6 +585,38 @@ int u2pl_pyramid_pool_fwd_f32(const float* x, long ldx, int N, int H, int W, int
 int u2pl_pyramid_pool_bwd_f32(const float* g0, long ldg0, const float* g1, long ldg1, const float* g2, long ldg2,
                               const float* g3, long ldg3, const float* add, long ldadd, int N, int H, int W, int C,
                               int b0, int b1, int b2, int b3, float* dx, long lddx, hipStream_t stream);
+/* Object-contextual representations (csrc/ocr.hip; OCRNet, Yuan et al. 2020).  Channel-wide tensors are NHWC rows: x, add, dx
+   [N*HW][C]; q, g_y, y, dq [N*HW][D]; region-side f, g_f [N*K][C] and kk, v, dk, dv [N*K][D] (a [N, C, K, 1] activation).  K-wide
+   tensors s, m, ds, w are [N*HW][K].  1 <= K <= 255, C % 4 == 0 (D likewise), N*HW < 2^31.  Channel-wide tensors: pitch a
+   multiple of 4 and >= the row width, base 16-byte aligned (float4 accesses).  K-wide tensors are accessed by single floats:
+   any pitch >= K (class logits of 19 classes come with pitch 19).  ws: caller-allocated floats, 16-byte aligned, at least what
+   the _ws_floats query of the entry point returns (0 for a shape out of contract); its contents on entry do not matter.  A
+   violation returns 1001 before any launch and leaves the outputs untouched.  Exact fp32, fixed summation order (first comment
+   block of csrc/ocr.hip), no atomics, no memset: the same bits on every run.
+   region pool forward ("spatial gather"): m[n,p,k] = softmax over the pixels p of image n of scale * s[n,p,k] (max-subtracted),
+   f[n,k,:] = sum_p m[n,p,k] x[n,p,:].  Both are written. */
+size_t u2pl_region_pool_fwd_ws_floats(int N, int HW, int K, int C);
+int u2pl_region_pool_fwd_f32(const float* s, long lds, const float* x, long ldx, float scale, int N, int HW, int K, int C,
+                             float* m, long ldm, float* f, long ldf, float* ws, hipStream_t stream);
+/* its backward: dx[n,p,:] = sum_k m[n,p,k] g_f[n,k,:] (+ add[n,p,:], the gradient x receives from its other consumer; null: none),
+   written exactly once; ds[n,p,k] = scale * m[n,p,k] * (g_f[n,k,:] . x[n,p,:] - c[n,k]), c[n,k] = g_f[n,k,:] . f[n,k,:] (equal to
+   sum_p m (g_f . x): one pass over the pixels).  m and f are the forward's outputs.  A null g_f (no gradient reached f) gives
+   dx = add (or 0) and ds = 0; x and f are then not read.  dx or ds may be null (that output is skipped), not both. */
+size_t u2pl_region_pool_bwd_ws_floats(int N, int HW, int K, int C);
+int u2pl_region_pool_bwd_f32(const float* g_f, long ldg, const float* m, long ldm, const float* x, long ldx, const float* f,
+                             long ldf, const float* add, long ldadd, float scale, int N, int HW, int K, int C, float* dx,
+                             long lddx, float* ds, long ldds, float* ws, hipStream_t stream);
+/* region attention forward: w[n,p,:] = softmax over k of scale * q[n,p,:] . kk[n,k,:], y[n,p,:] = sum_k w[n,p,k] v[n,k,:].  Both
+   are written.  No workspace. */
+int u2pl_region_attn_fwd_f32(const float* q, long ldq, const float* kk, long ldk, const float* v, long ldv, float scale, int N,
+                             int HW, int K, int D, float* w, long ldw, float* y, long ldy, hipStream_t stream);
+/* its backward, from g_y and the saved w: dv[n,k,:] = sum_p w g_y; dw = g_y . v; e = scale * w * (dw - sum_k w dw);
+   dq[n,p,:] = sum_k e kk[n,k,:]; dk[n,k,:] = sum_p e q[n,p,:].  Each of dq, dk, dv may be null (skipped), not all three; q is
+   read only for dk. */
+size_t u2pl_region_attn_bwd_ws_floats(int N, int HW, int K, int D);
+int u2pl_region_attn_bwd_f32(const float* g_y, long ldg, const float* w, long ldw, const float* q, long ldq, const float* kk,
+                             long ldk, const float* v, long ldv, float scale, int N, int HW, int K, int D, float* dq, long lddq,
+                             float* dk, long lddk, float* dv, long lddv, float* ws, hipStream_t stream);
 /* torch.cat / slices (base.py:99, decoder.py:117), 1x1 -> HxW bilinear broadcast (base.py:92-94) */
 int u2pl_copy_rows_f32(const float* src, long lds, float* dst, long ldd, long M, int C, int accumulate,
                        hipStream_t stream);

@@ -1,7 +1,6 @@
-"""DeepLabv3 / DeepLabv3+ decoders and the auxiliary head (reference:
-u2pl/models/decoder.py), and a pyramid-pooling decoder (dec_pspnet).  nn.Sequential containers keep the reference's
-indices (``classifier.8.weight``); ReLU / Dropout2d entries are markers fused
-into the BatchNorm apply kernel by u2pl_amd.nn.run_seq."""
+"""DeepLabv3 / DeepLabv3+ decoders and the auxiliary head (reference: u2pl/models/decoder.py), a pyramid-pooling decoder
+(dec_pspnet) and an object-contextual one (dec_ocrnet).  nn.Sequential containers keep the reference's indices
+(``classifier.8.weight``); ReLU / Dropout2d entries are markers fused into the BatchNorm apply kernel by u2pl_amd.nn.run_seq."""
 import torch.nn as nn
 
 from .. import nn as K
@@ -117,6 +116,71 @@ class dec_pspnet(nn.Module):
         res = {"pred": self.classifier(feat)}
         if self.rep_head and need_rep:
             res["rep"] = K.run_seq(self.representation, feat)
+        return res
+
+
+def _unit1x1(in_planes, out_planes, norm_layer):
+    return [K.Conv2d(in_planes, out_planes, kernel_size=1, stride=1, padding=0, bias=False), norm_layer(out_planes),
+            nn.ReLU(inplace=True)]
+
+
+class dec_ocrnet(nn.Module):
+    """Object-contextual representations head (OCRNet, Yuan et al., ECCV 2020, section 3.2; no reference line: the reference has
+    the two ASPP heads only).  conv3x3: 3x3 to inner_planes -> norm -> ReLU, the pixel features; region: 1x1 to 256 -> norm ->
+    ReLU -> 1x1 to num_classes, the soft object regions, a coarse prediction on the decoder's input that the trainer supervises
+    on the labelled images (region_loss_weight; output key "region").  The region features f = sum over an image's pixels of
+    softmax_pixels(region) * pixel features (K.region_pool) are a [N, inner, K, 1] map; queries f_pixel(pixel features), keys
+    f_object(f), values f_down(f), one head: y = softmax_k(q . k / sqrt(key_planes)) v (K.region_attention); fuse: 1x1 over
+    cat(f_up(y), pixel features) -> norm -> ReLU -> Dropout2d(0.05); classifier: 1x1 with bias.  rep_head: dec_pspnet's
+    `representation` tower on the fused features.  Out of scope, refused or absent: more than 255 classes (regions), several
+    heads, pixel-to-pixel attention, a separable form, regions taken from the auxiliary head, OHEM on the region loss."""
+
+    def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=256, sync_bn=False, rep_head=False,
+                 region_loss_weight=0.4):
+        super().__init__()
+        K.check_region_shapes(1, 1, num_classes, inner_planes, "dec_ocrnet (num_classes regions, inner_planes channels)")
+        K.check_region_shapes(1, 1, num_classes, key_planes, "dec_ocrnet (num_classes regions, key_planes channels)")
+        if in_planes % 4:
+            raise ValueError("dec_ocrnet: in_planes (%d) must be a multiple of 4" % in_planes)
+        if not float(region_loss_weight) >= 0:
+            raise ValueError("dec_ocrnet: region_loss_weight must be >= 0, got %r" % (region_loss_weight,))
+        norm_layer = norm_layer_for(sync_bn)
+        self.rep_head = rep_head
+        self.key_planes = key_planes
+        self.region_loss_weight = float(region_loss_weight)
+        self.conv3x3 = nn.Sequential(
+            K.Conv2d(in_planes, inner_planes, kernel_size=3, stride=1, padding=1, dilation=1, bias=False),
+            norm_layer(inner_planes), nn.ReLU(inplace=True))
+        self.region = nn.Sequential(
+            *_unit1x1(in_planes, 256, norm_layer),
+            K.Conv2d(256, num_classes, kernel_size=1, stride=1, padding=0, bias=True))
+        self.f_pixel = nn.Sequential(*_unit1x1(inner_planes, key_planes, norm_layer), *_unit1x1(key_planes, key_planes, norm_layer))
+        self.f_object = nn.Sequential(*_unit1x1(inner_planes, key_planes, norm_layer), *_unit1x1(key_planes, key_planes, norm_layer))
+        self.f_down = nn.Sequential(*_unit1x1(inner_planes, key_planes, norm_layer))
+        self.f_up = nn.Sequential(*_unit1x1(key_planes, inner_planes, norm_layer))
+        self.fuse = nn.Sequential(*_unit1x1(2 * inner_planes, inner_planes, norm_layer), nn.Dropout2d(0.05))
+        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        if rep_head:
+            self.representation = nn.Sequential(
+                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
+                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
+                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+
+    def forward(self, x, need_rep=True):
+        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
+            x = x[-1]
+        feat = K.run_seq(self.conv3x3, x)
+        r = K.run_seq(self.region, x)
+        feat_p, f = K.region_pool(feat, r)
+        q = K.run_seq(self.f_pixel, feat_p)
+        # independent conv -> BN -> ReLU units on the region features: under a process group their statistics share one exchange
+        k1, v = K.conv_bn_group([(self.f_object[0], self.f_object[1], f, True, None), (self.f_down[0], self.f_down[1], f, True, None)])
+        kk = K.conv_bn(self.f_object[3], self.f_object[4], k1, relu=True)
+        y = K.run_seq(self.f_up, K.region_attention(q, kk, v, self.key_planes ** -0.5))
+        out = K.run_seq(self.fuse, K.cat_channels((y, feat_p)))
+        res = {"pred": self.classifier(out), "region": r}
+        if self.rep_head and need_rep:
+            res["rep"] = K.run_seq(self.representation, out)
         return res
 
 

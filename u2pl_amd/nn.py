@@ -1414,6 +1414,115 @@ def pyramid_pool(x, bins):
     return _PyramidPoolFn.apply(x, check_pyramid_bins(bins))
 
 
+REGION_MAX_K = 255
+
+
+def check_region_shapes(N, HW, K, C, what="region pool / attention"):
+    """what the u2pl_region_* entry points (csrc/ocr.hip) refuse with 1001, as a ValueError before any call: N images of HW
+    pixels, K regions, C channels (the key width D of the attention)"""
+    N, HW, K, C = int(N), int(HW), int(K), int(C)
+    if not 1 <= K <= REGION_MAX_K:
+        raise ValueError("%s: 1 <= regions <= %d, got %d (more regions than that is pixel-to-pixel attention, which this "
+                         "project does not have)" % (what, REGION_MAX_K, K))
+    if C < 4 or C % 4:
+        raise ValueError("%s: channels must be a positive multiple of 4 (float4 rows), got %d" % (what, C))
+    if N < 1 or HW < 1 or N * HW >= 2 ** 31:
+        raise ValueError("%s: 1 <= N * H * W < 2^31, got %d x %d" % (what, N, HW))
+    return N, HW, K, C
+
+
+def _f32_ws(nfloats, device):
+    return torch.empty(max(int(nfloats), 4), dtype=torch.float32, device=device)
+
+
+class _RegionPoolFn(torch.autograd.Function):
+    """OCR's "spatial gather" (csrc/ocr.hip): m = softmax over the pixels of each image of scale * s, f = sum_p m x, plus x itself
+    handed through (the _PyramidPoolFn pattern): the gradient of the pass-through output reaches backward() together with f's
+    and goes into the backward kernel as `add`, so dx is written once.  m and f are saved; ds comes from the same launch."""
+
+    @staticmethod
+    def forward(ctx, x, s, scale):
+        xr, ldx = as_rows(x)
+        sr, lds = as_rows(s)
+        N, C, H, W = xr.shape
+        Kr = sr.shape[1]
+        if sr.shape[0] != N or tuple(sr.shape[2:]) != (H, W):
+            raise ValueError("region_pool: x %r and s %r are not maps of the same images" % (tuple(x.shape), tuple(s.shape)))
+        check_region_shapes(N, H * W, Kr, C, "region_pool")
+        m = torch.empty((N * H * W, Kr), dtype=torch.float32, device=xr.device)
+        f = new_act(N, C, Kr, 1, xr.device)
+        ws = _f32_ws(query("u2pl_region_pool_fwd_ws_floats", N, H * W, Kr, C), xr.device)
+        call("u2pl_region_pool_fwd_f32", sr, lds, xr, ldx, scale, N, H * W, Kr, C, m, Kr, f, C, ws)
+        ctx.save_for_backward(xr, m, f)
+        ctx.meta = (N, C, H, W, Kr, ldx, scale)
+        ctx.set_materialize_grads(False)
+        return x, f         # (an input returned as it is becomes an output of this node that aliases it)
+
+    @staticmethod
+    def backward(ctx, g_pass, g_f):
+        N, C, H, W, Kr, ldx, scale = ctx.meta
+        need_dx, need_ds = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_f is None or not (need_dx or need_ds):
+            return (g_pass if need_dx else None), None, None      # nothing reached f: dx is the other consumer's gradient, ds = 0
+        xr, m, f = ctx.saved_tensors
+        g, ldg = as_rows(g_f)
+        add, ldadd = (None, C) if g_pass is None else as_rows(g_pass)
+        dx = new_act(N, C, H, W, g.device) if need_dx else None
+        ds = new_act(N, Kr, H, W, g.device) if need_ds else None
+        ws = _f32_ws(query("u2pl_region_pool_bwd_ws_floats", N, H * W, Kr, C), g.device)
+        call("u2pl_region_pool_bwd_f32", g, ldg, m, Kr, xr, ldx, f, C, add, ldadd, scale, N, H * W, Kr, C, dx, C, ds, Kr, ws)
+        return dx, ds, None
+
+
+def region_pool(x, s, scale=1.0):
+    """-> (x_pass, f): f [N, C, K, 1], f[n, :, k] = sum_p softmax_p(scale * s[n, k])[p] * x[n, :, p] for s [N, K, H, W] and
+    x [N, C, H, W]; x_pass is x through the same autograd node (give IT, not x, to x's other consumers)."""
+    return _RegionPoolFn.apply(x, s, float(scale))
+
+
+class _RegionAttnFn(torch.autograd.Function):
+    """softmax(scale * q . kk) v over the K regions of each image, per pixel (csrc/ocr.hip); saves the weights w."""
+
+    @staticmethod
+    def forward(ctx, q, kk, v, scale):
+        qr, ldq = as_rows(q)
+        kr, ldk = as_rows(kk)
+        vr, ldv = as_rows(v)
+        N, D, H, W = qr.shape
+        Kr = kr.shape[2] * kr.shape[3]
+        if tuple(kr.shape) != tuple(vr.shape) or kr.shape[:2] != (N, D):
+            raise ValueError("region_attention: q %r, keys %r and values %r do not fit" % (tuple(q.shape), tuple(kk.shape),
+                                                                                          tuple(v.shape)))
+        check_region_shapes(N, H * W, Kr, D, "region_attention")
+        w = torch.empty((N * H * W, Kr), dtype=torch.float32, device=qr.device)
+        y = new_act(N, D, H, W, qr.device)
+        call("u2pl_region_attn_fwd_f32", qr, ldq, kr, ldk, vr, ldv, scale, N, H * W, Kr, D, w, Kr, y, D)
+        ctx.save_for_backward(qr, kr, vr, w)
+        ctx.meta = (N, D, H, W, Kr, ldq, ldk, ldv, scale, tuple(kk.shape))
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None or not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None
+        N, D, H, W, Kr, ldq, ldk, ldv, scale, kshape = ctx.meta
+        qr, kr, vr, w = ctx.saved_tensors
+        g, ldg = as_rows(gy)
+        dq = new_act(N, D, H, W, g.device) if ctx.needs_input_grad[0] else None
+        dk = new_act(*kshape, g.device) if ctx.needs_input_grad[1] else None
+        dv = new_act(*kshape, g.device) if ctx.needs_input_grad[2] else None
+        ws = _f32_ws(query("u2pl_region_attn_bwd_ws_floats", N, H * W, Kr, D), g.device)
+        call("u2pl_region_attn_bwd_f32", g, ldg, w, Kr, qr, ldq, kr, ldk, vr, ldv, scale, N, H * W, Kr, D, dq, D, dk, D, dv, D, ws)
+        return dq, dk, dv, None
+
+
+def region_attention(q, kk, v, scale):
+    """-> y [N, D, H, W] = sum_k softmax_k(scale * q . kk[:, :, k]) v[:, :, k] for q [N, D, H, W] and keys / values
+    [N, D, K, 1]: every pixel attends to the K regions of its own image (one head; K <= 255)."""
+    return _RegionAttnFn.apply(q, kk, v, float(scale))
+
+
 class _BroadcastFn(torch.autograd.Function):
     """bilinear(align_corners=True) up-sampling of a 1x1 map == broadcast (base.py:92-94)."""
 

@@ -105,6 +105,17 @@ def head_lr_times(d):
     return 10 if d["type"].startswith("pascal") else 1
 
 
+def add_region_loss(sup_loss, model, outs, B, hw, label_l, cfg):
+    """dec_ocrnet's soft object regions are a coarse prediction: when the outputs carry "region" and the decoder's
+    region_loss_weight is > 0, the first B (labelled) images are supervised with plain cross entropy -- also under OHEM
+    configs -- scaled by that weight.  Any other model: sup_loss as it is, no call made."""
+    weight = getattr(getattr(model, "decoder", None), "region_loss_weight", 0)
+    if "region" not in outs or not weight > 0:
+        return sup_loss
+    region = H.bilinear_up(outs["region"][:B], hw)
+    return sup_loss + H.cross_entropy(region, label_l, cfg["dataset"]["ignore_label"], scale=float(weight))
+
+
 class SemiTrainer:
     def __init__(self, cfg, model, model_teacher, sup_loss_fn, steps_per_epoch, memobank=None):
         self.cfg = cfg
@@ -299,6 +310,7 @@ class SemiTrainer:
                 sup_loss = self.sup_loss_fn([pred, aux], label_l)
             else:
                 sup_loss = self.sup_loss_fn(pred, label_l)
+            sup_loss = add_region_loss(sup_loss, model, outs, B, (h, w), label_l, cfg)
             teacher.train()
             with torch.no_grad():
                 teacher(image_l)
@@ -367,6 +379,7 @@ class SemiTrainer:
                 sup_loss = self.sup_loss_fn([pred_l_large, aux], label_l.clone())
             else:
                 sup_loss = self.sup_loss_fn(pred_l_large, label_l.clone())
+            sup_loss = add_region_loss(sup_loss, model, outs, B, (h, w), label_l, cfg)
             self._mark("student_fwd")        # incl. the supervised loss heads (bilinear up + OHEM / CE)
             main.wait_stream(side)
             K._lib.SIDE_WORK.discard("teacher")
@@ -474,6 +487,7 @@ class SupTrainer:
             loss = self.sup_loss_fn([pred, H.bilinear_up(outs["aux"], (h, w))], label)
         else:
             loss = self.sup_loss_fn(pred, label)
+        loss = add_region_loss(loss, self.model, outs, image.shape[0], (h, w), label, self.cfg)
         loss.backward()
         K.wgrad_stream_sync()
         W = _world()
