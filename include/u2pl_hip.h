@@ -149,6 +149,34 @@ int u2pl_scatter_rows_ordered_f32(float* dst, long ld, int D, const int* pix, co
                                   const int* order, const int* seg_pos, const int* seg_len, const float* src, long n,
                                   const float* gout_dev, float scale, hipStream_t stream);
 int u2pl_zero_rows_f32(float* dst, long ld, int D, const int* pix, long n, hipStream_t stream);
+/* Phase 2's sampling plan on the device (loss_helper.py:156-196; single rank, C <= 32, Q <= 1024): from the phase-1 list
+ * lengths (counts_dev, uint32 [3][32]) and the device-resident bank state (after u2pl_bank_enqueue_f32) it writes what
+ * the host builds after reading the lengths back: the valid classes (counts[1][c] > 0, loss_helper.py:156-158) and
+ * their number, the jobs in class order (position i of the valid list has candidates and class valid[i] has keys,
+ * loss_helper.py:176-178; the candidates are those of the POSITION, loss_helper.py:179), each job's descriptor
+ * (u2pl_infonce_job_bytes), its index draws idx_out[j][Q + Q K] = words[j (Q + Q K) + k] % bound (torch.randint on the CPU
+ * generator is raw mt19937 word % high, loss_helper.py:179-196; words: C (Q + Q K) raw words uploaded by the host), and
+ * the anchors' grouping of hipops.group_entries (groups: int [3][C Q] order / seg_pos / seg_len).  anchor_pix [C Q]: -1
+ * for the entries of absent jobs.  plan_hdr (u2pl_infonce_plan_hdr_bytes): {njobs, valid_seg, (float)(1 / valid_seg),
+ * (float)(1 / (Q valid_seg)), njobs Q}; njobs = 0 when valid_seg <= 1 (loss_helper.py:160-162) and *loss = 0.0f.
+ * mirror: uint32 [3 * 32 + 2] on the device = the counts, njobs, valid_seg, for the host to copy back when it likes. */
+size_t u2pl_infonce_plan_hdr_bytes(void);
+int u2pl_infonce_plan(const unsigned* counts_dev, const long long* bank_state, const unsigned* words, int C, int Q, int K,
+                      const int* lists, long list_stride, const float* proto, int D, const float* storage, void* jobs_dev,
+                      long long* idx_out, int* groups, int* anchor_pix, void* plan_hdr, unsigned* mirror, float* loss,
+                      hipStream_t stream);
+/* u2pl_infonce_fused_f32 (loss_helper.py:173-233) with the job count and 1 / valid_seg taken from plan_hdr: grid of
+ * max_jobs jobs, blocks of absent jobs only clear their stale row; per-job buffers sized for max_jobs; same arithmetic
+ * and summation order for the jobs that exist.  No job: *loss keeps the 0.0f u2pl_infonce_plan wrote. */
+int u2pl_infonce_fused_dev_f32(const void* jobs_dev, const void* plan_hdr, int max_jobs, const float* rep, long ld, int D,
+                               int Q, int K, float temp, float* loss_q, float* ganchor, int* anchor_pix, int* head,
+                               int* next, const int* seg_len, float* zero_dst, long zero_ld, const int* zero_pix,
+                               long zero_n, void* workspace, float* loss, hipStream_t stream);
+/* u2pl_scatter_rows_ordered_f32 (loss_helper.py:205-230 backward) with n = njobs Q and scale = 1 / (Q valid_seg) taken
+ * from plan_hdr; max_n = max_jobs Q sizes the grid */
+int u2pl_scatter_rows_ordered_dev_f32(float* dst, long ld, int D, const int* pix, const int* next, int* head,
+                                      const int* order, const int* seg_pos, const int* seg_len, const float* src,
+                                      long max_n, const float* gout_dev, const void* plan_hdr, hipStream_t stream);
 
 /* ---- losses.hip ----------------------------------------------------------- */
 /* F.cross_entropy(ignore_index=255) fwd/bwd: loss_helper.py:46, 295-320, 531 */

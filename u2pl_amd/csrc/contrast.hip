@@ -927,9 +927,18 @@ struct NceJob {
 //     sum of its four anchors (write-through store), takes a ticket (32 shards, then one top counter: ~40 same-address
 //     atomics in a row instead of 1216), and the block that completes the top counter adds the 1216 partials in a fixed
 //     order (bit-reproducible) and writes the loss.  The counters are left at zero for the next launch.
+//   plan: the header words of u2pl_infonce_plan (NcePlanHdr) when the job count and the loss scale live on the device
+//     (u2pl_infonce_fused_dev_f32): the grid is the worst case, blocks of absent jobs clear their stale row and leave
+struct NcePlanHdr {
+    int njobs, valid_seg;       // jobs of this step (0 when valid_seg <= 1: the loss is 0, loss_helper.py:160-162)
+    float inv_valid_seg;        // (float)(1.0 / valid_seg)
+    float bwd_scale;            // (float)(1.0 / (Q * valid_seg))
+    int entries, pad_[3];       // njobs * Q
+};
 struct NceExtra {
     float* zero_dst; long zero_ld; const int* zero_pix; long zero_n;
     float* partial; unsigned* ticket; float* loss; double scale;
+    const NcePlanHdr* plan;
 };
 __device__ __forceinline__ void nce_ld4(const float* p0, const float* p1, const float* p2, const float* p3, float (&v)[4]) {
     // four independent loads past the L1 (sc1), waited for once (chains of atomic loads are issued two per round trip)
@@ -950,6 +959,23 @@ __global__ void k_infonce(const NceJob* __restrict__ jobs, const float* __restri
     int zpix = -1;
     if (X.zero_dst && zw < X.zero_n) zpix = ldg(X.zero_pix + zw);
     if (q >= Q) return;      // (never taken on the fused path: the host requires Q % 4 == 0 there)
+    // stale gradient rows of the previous step: one 1 KiB row per wave (D <= 256: 16 bytes per lane); entries of absent jobs are -1
+    auto clear_stale = [&]() {
+        if (!X.zero_dst) return;
+        const long nw = (long)gridDim.x * gridDim.y * (blockDim.x >> 6);
+        if (zpix >= 0 && lane * 4 < D) *(float4*)(X.zero_dst + (long)zpix * X.zero_ld + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (long r = zw + nw; r < X.zero_n; r += nw) {     // (more stale rows than waves: only when the previous step had more jobs)
+            const int zp = X.zero_pix[r];
+            if (zp >= 0 && lane * 4 < D) *(float4*)(X.zero_dst + (long)zp * X.zero_ld + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    unsigned njobs_live = gridDim.y;
+    double loss_scale = X.scale;
+    if (X.plan) {            // job count and scale from the planning kernel: block-uniform scalar loads
+        njobs_live = (unsigned)X.plan->njobs;
+        if ((unsigned)job >= njobs_live) { clear_stale(); return; }
+        loss_scale = (double)X.plan->inv_valid_seg / (double)Q;
+    }
     const NceJob J = jobs[job];
     // Two dependent address chains start here: anchor = rep[cand[idx_a[q]]] (three loads deep) and the sampled bank rows
     // bank[slot(idx_n[q][j])] (two deep).  Both index loads are issued back to back, and the first four feature rows are
@@ -1098,7 +1124,7 @@ __global__ void k_infonce(const NceJob* __restrict__ jobs, const float* __restri
         if (lane == 0) sl[threadIdx.x >> 6] = lse - l0;
         __syncthreads();
         if (threadIdx.x == 0) {
-            const unsigned gb = (unsigned)job * gridDim.x + blockIdx.x, nb = gridDim.x * gridDim.y;
+            const unsigned gb = (unsigned)job * gridDim.x + blockIdx.x, nb = gridDim.x * njobs_live;
             __hip_atomic_store(X.partial + gb, (sl[0] + sl[1]) + (sl[2] + sl[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // written through before the ticket
             const unsigned sh = gb & 31u, nsh = (nb - sh + 31u) / 32u, nshards = nb < 32u ? nb : 32u;
@@ -1115,7 +1141,7 @@ __global__ void k_infonce(const NceJob* __restrict__ jobs, const float* __restri
         __syncthreads();
         if (s_last) {      // every partial has been written through: add them in a fixed order
             __shared__ double sred[256];
-            const int nb = gridDim.x * gridDim.y;
+            const int nb = (int)(gridDim.x * njobs_live);
             double acc = 0.0;
             for (int i0 = 0; i0 < nb; i0 += 4 * 256) {
                 float v[4];
@@ -1131,7 +1157,7 @@ __global__ void k_infonce(const NceJob* __restrict__ jobs, const float* __restri
                 if ((int)threadIdx.x < o) sred[threadIdx.x] += sred[threadIdx.x + o];
                 __syncthreads();
             }
-            if (threadIdx.x == 0) *X.loss = (float)(sred[0] * X.scale);
+            if (threadIdx.x == 0) *X.loss = (float)(sred[0] * loss_scale);
         }
     }
     if (lane == 0) {
@@ -1151,12 +1177,7 @@ __global__ void k_infonce(const NceJob* __restrict__ jobs, const float* __restri
 #pragma unroll
     for (int i = 0; i < VPL; ++i)
         g[i] = inv_temp * ((acc[i] * inv_s - f0h[i]) - cosbar * ah[i]) * na;
-    if (X.zero_dst) {      // stale gradient rows of the previous step: one 1 KiB row per wave (D <= 256: 16 bytes per lane)
-        const long nw = (long)gridDim.x * gridDim.y * (blockDim.x >> 6);
-        if (zpix >= 0 && lane * 4 < D) *(float4*)(X.zero_dst + (long)zpix * X.zero_ld + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (long r = zw + nw; r < X.zero_n; r += nw)       // (more stale rows than waves: only when the previous step had more jobs)
-            if (lane * 4 < D) *(float4*)(X.zero_dst + (long)X.zero_pix[r] * X.zero_ld + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    clear_stale();
 }
 
 static int nce_launch(const void* jobs_dev, int njobs, const float* rep, long ld, int D, int Q, int K, float temp,
@@ -1216,6 +1237,140 @@ static int nce_launch(const void* jobs_dev, int njobs, const float* rep, long ld
     return 0;
 }
 U2PL_API size_t u2pl_infonce_job_bytes(void) { return sizeof(NceJob); }
+// the fused launch with the job count and the loss scale read from the planning kernel's header: the grid is the worst
+// case (max_jobs), blocks of absent jobs only clear their stale row.  The ticket counts njobs * Q / 4 blocks, so the
+// partials are added in the order u2pl_infonce_fused_f32 adds them for the same jobs.  No job: no block writes *loss
+// (u2pl_infonce_plan stored 0.0f there).
+U2PL_API int u2pl_infonce_fused_dev_f32(const void* jobs_dev, const void* plan_hdr, int max_jobs, const float* rep, long ld,
+                                        int D, int Q, int K, float temp, float* loss_q, float* ganchor, int* anchor_pix,
+                                        int* head, int* next, const int* seg_len, float* zero_dst, long zero_ld,
+                                        const int* zero_pix, long zero_n, void* workspace, float* loss, hipStream_t stream) {
+    if (Q % 4 || !workspace || !loss || D > 256 || !plan_hdr || max_jobs <= 0 || max_jobs > MAXC) return U2PL_EINVAL;
+    NceExtra X = {};
+    if (zero_dst && zero_pix && zero_n > 0) { X.zero_dst = zero_dst; X.zero_ld = zero_ld; X.zero_pix = zero_pix; X.zero_n = zero_n; }
+    X.ticket = (unsigned*)workspace;
+    X.partial = (float*)workspace + 64;
+    X.loss = loss;
+    X.plan = (const NcePlanHdr*)plan_hdr;
+    return nce_launch(jobs_dev, max_jobs, rep, ld, D, Q, K, temp, loss_q, ganchor, anchor_pix, head, next, seg_len, X, stream);
+}
+
+// ---------------------------------------------------------------------------
+// The sampling plan of phase 2 on the device (loss_helper.py:156-196): which classes are valid, which of them have a
+// job, every job's descriptor, its index draws and the grouping of its anchors -- what hipops.infonce_loss and
+// hipops.group_entries build on the host once the list lengths have been read back.  The draws are
+// torch.randint(high, (n,)) of the CPU generator, i.e. word % high over consecutive raw 32-bit mt19937 words: the host
+// uploads the raw words (they do not depend on the lengths), the bounds are applied here.  Job j consumes the words
+// [j * (Q + Q K), (j + 1) * (Q + Q K)): Q anchors, then Q K negatives.
+//   grid (PLAN_BX, C): row y is job y; block (0, 0) also writes the header, the host's mirror words and *loss = 0
+//   block x == 0 of a job: descriptor, anchor draws, stable rank-by-counting sort of the Q anchors (Q <= PLAN_MAXQ)
+//   every block of a job: a slice of the Q K negative draws
+// ---------------------------------------------------------------------------
+#define PLAN_T 256
+#define PLAN_BX 8
+#define PLAN_MAXQ 1024
+__global__ __launch_bounds__(PLAN_T) void k_infonce_plan(const unsigned* __restrict__ counts, const long long* __restrict__ state,
+                                                         const unsigned* __restrict__ words, int C, int Q, int K,
+                                                         const int* __restrict__ lists, long list_stride,
+                                                         const float* __restrict__ proto, int D, const float* __restrict__ storage,
+                                                         NceJob* __restrict__ jobs, long long* __restrict__ idx_out,
+                                                         int* __restrict__ groups, int* __restrict__ anchor_pix,
+                                                         NcePlanHdr* __restrict__ hdr, unsigned* __restrict__ mirror,
+                                                         float* __restrict__ loss) {
+    __shared__ int s_pos[MAXC], s_cls[MAXC], s_nj, s_nv;
+    __shared__ unsigned s_ia[PLAN_MAXQ];
+    const int j = blockIdx.y, tid = threadIdx.x;
+    if (tid == 0) {          // <= 32 classes: one thread walks them (every block repeats the walk: no grid-wide exchange)
+        int valid[MAXC], nv = 0, nj = 0;
+        for (int c = 0; c < C; ++c)
+            if (counts[MAXC + c] > 0) valid[nv++] = c;
+        for (int i = 0; i < nv; ++i) {       // Q1: the candidates of POSITION i, the bank of class valid[i]
+            const int vc = valid[i];
+            if (counts[i] > 0 && state[5 * vc + 3] > 0) { s_pos[nj] = i; s_cls[nj] = vc; ++nj; }
+        }
+        s_nv = nv;
+        s_nj = nv <= 1 ? 0 : nj;             // loss_helper.py:160-162: at most one valid class -> 0 * rep.sum()
+    }
+    __syncthreads();
+    const int nj = s_nj;
+    if (blockIdx.x == 0 && j == 0) {
+        if (tid < 3 * MAXC) mirror[tid] = counts[tid];
+        if (tid == 0) {
+            const int nv = s_nv;
+            mirror[3 * MAXC] = (unsigned)nj;
+            mirror[3 * MAXC + 1] = (unsigned)nv;
+            NcePlanHdr h = {};
+            h.njobs = nj;
+            h.valid_seg = nv;
+            h.inv_valid_seg = nv > 0 ? (float)(1.0 / (double)nv) : 0.f;
+            h.bwd_scale = nv > 0 ? (float)(1.0 / (double)((long)Q * nv)) : 0.f;
+            h.entries = nj * Q;
+            *hdr = h;
+            *loss = 0.0f;
+        }
+    }
+    if (j >= nj) {           // absent job: its entries of the pixel list read "no row" (the next step's stale-row clearing skips them)
+        if (blockIdx.x == 0)
+            for (int q = tid; q < Q; q += PLAN_T) anchor_pix[(long)j * Q + q] = -1;
+        return;
+    }
+    const int pos = s_pos[j], vc = s_cls[j];
+    const unsigned ncand = counts[pos];
+    const unsigned blen = (unsigned)state[5 * vc + 3];
+    const long per = (long)Q + (long)Q * K, off = (long)j * per;
+    const long QK = (long)Q * K;
+    for (long k = (long)blockIdx.x * PLAN_T + tid; k < QK; k += (long)PLAN_BX * PLAN_T)
+        idx_out[off + Q + k] = (long long)(words[off + Q + k] % blen);
+    if (blockIdx.x != 0) return;
+    if (tid == 0) {
+        NceJob J;
+        J.cand = lists + (long)pos * list_stride;
+        J.idx_a = idx_out + off;
+        J.idx_n = idx_out + off + Q;
+        J.proto = proto + (long)pos * D;
+        J.bank = storage + state[5 * vc + 0] * D;
+        J.bank_cap = state[5 * vc + 1];
+        J.bank_head = state[5 * vc + 2];
+        jobs[j] = J;
+    }
+    for (int q = tid; q < Q; q += PLAN_T) {
+        const unsigned ia = words[off + q] % ncand;
+        s_ia[q] = ia;
+        idx_out[off + q] = (long long)ia;
+    }
+    __syncthreads();
+    // np.argsort(kind="stable") of the Q draws by counting: rank = (smaller draws) + (equal draws before this one); the
+    // first of a group of equal draws is its leader, at position `smaller`, with the group's size
+    const long CQ = (long)gridDim.y * Q;
+    for (int q = tid; q < Q; q += PLAN_T) {
+        const unsigned v = s_ia[q];
+        int less = 0, eq = 0, eq_before = 0;
+        for (int p = 0; p < Q; ++p) {
+            const unsigned u = s_ia[p];
+            less += u < v;
+            eq += u == v;
+            eq_before += (u == v) & (p < q);
+        }
+        const int e = j * Q + q;
+        groups[(long)j * Q + less + eq_before] = e;
+        groups[CQ + e] = eq_before == 0 ? j * Q + less : 0;
+        groups[2 * CQ + e] = eq_before == 0 ? eq : 0;
+    }
+}
+U2PL_API size_t u2pl_infonce_plan_hdr_bytes(void) { return sizeof(NcePlanHdr); }
+U2PL_API int u2pl_infonce_plan(const unsigned* counts_dev, const long long* bank_state, const unsigned* words, int C, int Q,
+                               int K, const int* lists, long list_stride, const float* proto, int D, const float* storage,
+                               void* jobs_dev, long long* idx_out, int* groups, int* anchor_pix, void* plan_hdr,
+                               unsigned* mirror, float* loss, hipStream_t stream) {
+    if (C <= 0 || C > MAXC || Q <= 0 || Q > PLAN_MAXQ || K <= 0 || !counts_dev || !bank_state || !words || !lists || !proto ||
+        !storage || !jobs_dev || !idx_out || !groups || !anchor_pix || !plan_hdr || !mirror || !loss)
+        return U2PL_EINVAL;
+    U2PL_LAUNCH(k_infonce_plan, dim3(PLAN_BX, C), dim3(PLAN_T), 0, stream, counts_dev, bank_state, words, C, Q, K, lists,
+                list_stride, proto, D, storage, (NceJob*)jobs_dev, idx_out, groups, anchor_pix, (NcePlanHdr*)plan_hdr, mirror,
+                loss);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
 
 // loss = (sum_jobs mean_q loss_q) / valid_seg = sum_all loss_q / (Q * valid_seg)   (loss_helper.py:228-233)
 // one 1024-thread block, fixed summation order (deterministic), double accumulation.  Q % 4 == 0: the arithmetic of the
@@ -1269,8 +1424,10 @@ __global__ __launch_bounds__(256) void k_scatter_rows_ordered(float* __restrict_
                                                               int* __restrict__ head, const int* __restrict__ order,
                                                               const int* __restrict__ seg_pos, const int* __restrict__ seg_len,
                                                               const float* __restrict__ src, int n,
-                                                              const float* __restrict__ gout, float scale) {
+                                                              const float* __restrict__ gout, float scale,
+                                                              const NcePlanHdr* __restrict__ plan) {
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (plan) { n = plan->entries; scale = plan->bwd_scale; }      // device-planned step: n is the worst case until here
     if (e >= n) return;
     // Everything that is indexed by the entry itself is requested at once, then everything that hangs off those values:
     // three dependent round trips on the common path (a leader that is alone in its chain) instead of seven
@@ -1326,7 +1483,19 @@ U2PL_API int u2pl_scatter_rows_ordered_f32(float* dst, long ld, int D, const int
     if (n <= 0) return 0;
     if (D % 4 || D > 256) return U2PL_EINVAL;
     U2PL_LAUNCH(k_scatter_rows_ordered, dim3(cdiv(n, 4)), dim3(256), 0, stream, dst, ld, D, pix, next, head, order,
-                       seg_pos, seg_len, src, (int)n, gout_dev, scale);
+                       seg_pos, seg_len, src, (int)n, gout_dev, scale, (const NcePlanHdr*)nullptr);
+    U2PL_LAUNCH_CHECK();
+    return 0;
+}
+// the same with the entry count (njobs * Q) and the scale 1 / (Q * valid_seg) read from u2pl_infonce_plan's header; max_n:
+// the worst-case entry count the grid covers (waves past the step's entries leave after one scalar load)
+U2PL_API int u2pl_scatter_rows_ordered_dev_f32(float* dst, long ld, int D, const int* pix, const int* next, int* head,
+                                               const int* order, const int* seg_pos, const int* seg_len, const float* src,
+                                               long max_n, const float* gout_dev, const void* plan_hdr, hipStream_t stream) {
+    if (max_n <= 0) return 0;
+    if (D % 4 || D > 256 || !plan_hdr) return U2PL_EINVAL;
+    U2PL_LAUNCH(k_scatter_rows_ordered, dim3(cdiv(max_n, 4)), dim3(256), 0, stream, dst, ld, D, pix, next, head, order,
+                       seg_pos, seg_len, src, (int)max_n, gout_dev, 0.0f, (const NcePlanHdr*)plan_hdr);
     U2PL_LAUNCH_CHECK();
     return 0;
 }
@@ -1334,7 +1503,8 @@ __global__ void k_zero_rows(float* __restrict__ dst, long ld, int D, const int* 
     const int D4 = D >> 2;
     const long total = n * D4;
     for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x)
-        *(float4*)(dst + (long)pix[t / D4] * ld + 4 * (t % D4)) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pix[t / D4] >= 0)      // (entries of jobs a device-planned step did not have are -1)
+            *(float4*)(dst + (long)pix[t / D4] * ld + 4 * (t % D4)) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 U2PL_API int u2pl_zero_rows_f32(float* dst, long ld, int D, const int* pix, long n, hipStream_t stream) {
     if (n <= 0) return 0;

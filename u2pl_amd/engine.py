@@ -97,6 +97,8 @@ def load_state(path, model, optimizer=None, key="model_state"):
 
 def _rng_state():
     """the four RNG streams of a step as tensors / plain scalars only (torch.load(weights_only=True) accepts the file)"""
+    from . import hipops as H
+    H.settle_host_reads()       # (draws the device applied but the CPU generator has not consumed yet)
     kind, keys, pos, has_gauss, cached = np.random.get_state()
     ver, pk, gauss = random.getstate()
     return {"torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
@@ -109,6 +111,8 @@ def checkpoint_state(epoch, best, model, teacher, trainer):
     """train_semi.py:210-224 wire format (`module.`-prefixed model_state / teacher_state, torch-SGD optimizer_state,
     best_miou, epoch) + what upstream forgets and a bit-faithful resume needs: the memory bank, the iteration counter
     and the RNG streams (extra keys, ignored by the reference's load_state)."""
+    from . import hipops as H
+    H.settle_host_reads()       # (bank bookkeeping and generator of a step whose blocking read is still deferred)
     state = {"epoch": epoch, "model_state": state_dict_ddp(model), "optimizer_state": trainer.optimizer_state_dict(),
              "best_miou": best, "cur_iter": trainer.cur_iter,
              "rng_state": _rng_state()}
@@ -120,6 +124,8 @@ def checkpoint_state(epoch, best, model, teacher, trainer):
 
 
 def restore_extras(ckpt, trainer, steps_per_epoch):
+    from . import hipops as H
+    H.settle_host_reads()
     trainer.cur_iter = ckpt.get("cur_iter", ckpt.get("epoch", 0) * steps_per_epoch)
     if "optimizer_state" in ckpt:
         trainer.load_optimizer_state_dict(ckpt["optimizer_state"])

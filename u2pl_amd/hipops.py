@@ -487,6 +487,29 @@ def check_split(rs):
         _split_failed(rs)
 
 
+def defer_check_split(rs):
+    """check_split() for a step whose blocking read has been deferred (defer_host_read): the error word is copied to
+    pinned memory behind the kernel now and examined when the deferred reads are settled -- a direct read then would
+    wait for everything enqueued since"""
+    err = rs.get("err") if isinstance(rs, dict) else None
+    if err is None:
+        return
+    ring = _SPLIT_WATCH.get("deferred")
+    if ring is None:
+        ring = _SPLIT_WATCH["deferred"] = {"slots": [(torch.empty(1, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                                                     for _ in range(2)], "next": 0}
+    host, ev = ring["slots"][ring["next"]]
+    ring["next"] = (ring["next"] + 1) % len(ring["slots"])
+    host.copy_(err, non_blocking=True)
+    ev.record()
+
+    def examine():
+        ev.synchronize()
+        if int(host[0]) != 0:
+            _split_failed(rs)
+    defer_host_read(examine)
+
+
 def watch_split(rs):
     """check_split() for steps WITHOUT a host synchronisation (configs without trainer.contrastive are valid upstream):
     the error word is copied to pinned host memory behind the kernel (no stall) and examined by poll_split() at the
@@ -628,11 +651,50 @@ def unpack_class_bits(bits, C):
     return oh
 
 
+# --------------------------------------------------------------------------- deferred host read
+# With the contrastive sampling planned on the device (sampling_plan) the step's one device-to-host read -- the list
+# lengths -- is no longer needed to ENQUEUE the step; it is taken at the end of train_step.  Until then the host copies
+# that depend on it are stale: the memory bank's length / head / ptr, LAST_STATS and the global CPU generator (not yet
+# advanced by the draws).  Whoever reads one of them calls settle_host_reads() first; it is a no-op when nothing is pending.
+_SETTLE = []
+
+
+def defer_host_read(fn):
+    """fn runs at the next settle_host_reads(), after those deferred before it"""
+    _SETTLE.append(fn)
+
+
+def host_read_pending():
+    return bool(_SETTLE)
+
+
+def settle_host_reads():
+    while _SETTLE:
+        fns = list(_SETTLE)
+        del _SETTLE[:]       # (cleared first: what fn reads -- the bank's bookkeeping -- settles too)
+        for fn in fns:
+            fn()
+
+
+def _settled(name):
+    def get(self):
+        settle_host_reads()
+        return getattr(self, name)
+
+    def put(self, value):
+        settle_host_reads()
+        setattr(self, name, value)
+    return property(get, put)
+
+
 # --------------------------------------------------------------------------- memory bank
 class DeviceMemoryBank:
     """Per-class FIFO of negative keys resident in HBM (replaces the reference's
     list of CPU tensors, train_semi.py:161-169 / utils.py:27-47).  Logical row j
     of class c lives at physical slot (head[c] + j) % cap[c]."""
+
+    # host bookkeeping: reading it settles a deferred read of the list lengths first (settle_host_reads)
+    head, length, ptr = _settled("_head"), _settled("_length"), _settled("_ptr")
 
     def __init__(self, num_classes, queue_size, feat_dim=256, device="cuda"):
         check_num_classes(num_classes, "DeviceMemoryBank: num_classes")
@@ -928,7 +990,9 @@ def _nce_rearm(st):
     """a forward pass whose backward never ran (loss evaluated without gradients) left its chain heads armed: clear them
     before new chains are built on top (rare path, plain torch)"""
     if st["pending"] is not None:
-        st["head"].index_fill_(0, st["pending"].reshape(-1).long(), -1)
+        # (entries of jobs a device-planned step did not have are -1: clamped onto pixel 0, whose head is either armed by
+        # this same forward or -1 already)
+        st["head"].index_fill_(0, st["pending"].reshape(-1).long().clamp_min_(0), -1)
         st["pending"] = None
 
 
@@ -1026,6 +1090,125 @@ class _ZeroTimesSum(torch.autograd.Function):
 
 def zero_times_sum(rep):
     return _ZeroTimesSum.apply(rep)
+
+
+class _InfoNCEDev(torch.autograd.Function):
+    """_InfoNCE with the job count, the valid-class count and both scales on the device (plan: the buffers of
+    sampling_plan): worst-case grids, per-job buffers sized for max_jobs, no host value depends on the step's counts."""
+
+    @staticmethod
+    def forward(ctx, rep_rows, plan, Q, K, temp):
+        P, D = rep_rows.shape
+        dev = rep_rows.device
+        mj = plan["max_jobs"]
+        st = _nce_state(dev, P, D)
+        loss_q = torch.empty((mj, Q), dtype=torch.float32, device=dev)
+        ganchor = torch.empty((mj, Q, D), dtype=torch.float32, device=dev)
+        nxt = torch.empty((mj, Q), dtype=torch.int32, device=dev)
+        apix, groups = plan["apix"], plan["groups"]
+        _nce_rearm(st)
+        need = query("u2pl_infonce_fused_workspace_bytes", MAXC, Q)
+        if st["ws"] is None or st["ws"].numel() < need:
+            st["ws"] = torch.zeros(need, dtype=torch.uint8, device=dev)
+        dirty = st["dirty"]
+        call("u2pl_infonce_fused_dev_f32", plan["jobs"], plan["hdr"], mj, rep_rows, D, D, Q, K, float(temp), loss_q, ganchor,
+             apix, st["head"], nxt, groups[2], st["grad"] if dirty is not None else None, D, dirty,
+             dirty.numel() if dirty is not None else 0, st["ws"], plan["loss"])
+        st["dirty"] = None
+        st["pending"] = apix
+        ctx.save_for_backward(ganchor, apix, nxt, groups, plan["hdr"])
+        ctx.meta = (P, D, mj * Q)
+        return plan["loss"]
+
+    @staticmethod
+    def backward(ctx, g):
+        ganchor, apix, nxt, groups, hdr = ctx.saved_tensors
+        P, D, n = ctx.meta
+        st = _nce_state(g.device, P, D)
+        if st["pending"] is not apix:
+            raise _lib.HipError("InfoNCE backward must follow its own forward exactly once (the per-pixel chains are "
+                                "consumed by the backward pass; retain_graph / interleaved forwards are not supported)")
+        st["pending"] = None
+        if st["dirty"] is not None:
+            call("u2pl_zero_rows_f32", st["grad"], D, D, st["dirty"], st["dirty"].numel())
+        call("u2pl_scatter_rows_ordered_dev_f32", st["grad"], D, D, apix, nxt, st["head"], groups[0], groups[1], groups[2],
+             ganchor, n, g.contiguous(), hdr)
+        st["dirty"] = apix
+        return st["grad"], None, None, None, None
+
+
+_PLAN_HOST = {}
+
+
+def _plan_host_slot(n_words):
+    """pinned staging for the raw words and the mirror words, with the event that says the mirror has arrived.  Two slots
+    in turn: a slot's words are uploaded in one step and its mirror is read at the end of that step, before the slot
+    comes round again."""
+    ring = _PLAN_HOST.get(n_words)
+    if ring is None:
+        ring = _PLAN_HOST[n_words] = {"slots": [dict(words=torch.empty(n_words, dtype=torch.int32).pin_memory(),
+                                                      mirror=torch.zeros(3 * MAXC + 2, dtype=torch.int32).pin_memory(),
+                                                      event=torch.cuda.Event()) for _ in range(2)], "next": 0}
+    slot = ring["slots"][ring["next"]]
+    ring["next"] = (ring["next"] + 1) % len(ring["slots"])
+    return slot
+
+
+def sampling_device_ok(rep_rows, ph1, bank, cfg):
+    """the shapes u2pl_infonce_plan + u2pl_infonce_fused_dev_f32 are built for; every bound a draw can have (a list holds
+    at most P pixels, a ring at most its capacity) is below the generator's one-word limit"""
+    from . import rng_words as RW
+    Q, D = int(cfg["num_queries"]), rep_rows.shape[1]
+    return (NCE_FUSED and not ph1.wide and Q % 4 == 0 and 0 < Q <= 1024 and int(cfg["num_negatives"]) > 0 and D <= 256
+            and D in (64, 128, 256) and ph1.cap < RW.ONE_WORD_BOUND and max(bank.cap) < RW.ONE_WORD_BOUND)
+
+
+def sampling_plan(ph1, bank, C, Q, K, D, words=None):
+    """u2pl_infonce_plan on the current stream: raw words of the global CPU generator (not advanced), the plan's device
+    buffers, and the asynchronous copy of the mirror words to pinned memory.  -> dict of buffers + the host slot.
+    words (uint32 [C (Q + Q K)], tests): these instead of the generator's."""
+    from . import rng_words as RW
+    dev = ph1.counts.device
+    per = Q + Q * K
+    slot = _plan_host_slot(C * per)
+    if words is None:
+        words = RW.peek_words(C * per)
+    slot["words"].numpy()[:] = np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)
+    words = slot["words"].to(dev, non_blocking=True)
+    bank._sync_state()
+    plan = dict(max_jobs=C, per=per, slot=slot, words=words, ph1=ph1,
+                jobs=torch.empty((C, 7), dtype=torch.int64, device=dev),
+                idx=torch.empty((C, per), dtype=torch.int64, device=dev),
+                groups=torch.empty((3, C * Q), dtype=torch.int32, device=dev),
+                apix=torch.empty((C, Q), dtype=torch.int32, device=dev),
+                hdr=torch.empty(query("u2pl_infonce_plan_hdr_bytes") // 4, dtype=torch.int32, device=dev),
+                mirror=torch.empty(3 * MAXC + 2, dtype=torch.int32, device=dev),
+                loss=torch.empty((), dtype=torch.float32, device=dev))
+    assert query("u2pl_infonce_job_bytes") == 56
+    call("u2pl_infonce_plan", ph1.counts, bank.state, words, C, Q, K, ph1.idx, ph1.cap, ph1.proto, D, bank.storage,
+         plan["jobs"], plan["idx"], plan["groups"], plan["apix"], plan["hdr"], plan["mirror"], plan["loss"])
+    slot["mirror"].copy_(plan["mirror"], non_blocking=True)
+    slot["event"].record()
+    return plan
+
+
+def infonce_loss_device(rep_rows, ph1, bank, cfg, words=None):
+    """Phase 2 (loss_helper.py:156-233) without the host knowing the list lengths: plan, InfoNCE forward at the worst-case
+    grid.  -> (loss, plan); the loss is exactly 0 and its gradient all zeros when there is no job or at most one valid
+    class (what zero_times_sum gives on the host path)."""
+    Q, K = int(cfg["num_queries"]), int(cfg["num_negatives"])
+    plan = sampling_plan(ph1, bank, ph1.C, Q, K, rep_rows.shape[1], words)
+    loss = _InfoNCEDev.apply(rep_rows, plan, Q, K, float(cfg["temperature"]))
+    infonce_loss_device.last_plan = plan     # (tests and bench.py's replay look at the tables of the last step)
+    return loss, plan
+
+
+def plan_mirror(plan):
+    """wait for the plan's mirror words (they were copied right behind the planning kernel) -> counts uint32-valued
+    int64 [3][32], njobs, valid_seg"""
+    plan["slot"]["event"].synchronize()
+    m = plan["slot"]["mirror"].numpy().view(np.uint32).astype(np.int64)
+    return m[:3 * MAXC].reshape(3, MAXC), int(m[3 * MAXC]), int(m[3 * MAXC + 1])
 
 
 def infonce_loss(rep_rows, ph1, bank, valid_classes, counts_host, cfg, randint=None):

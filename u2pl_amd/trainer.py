@@ -7,7 +7,10 @@ three percentile thresholds are computed once and selected exactly on device,
 parameters / gradients / momentum live in flat arenas (one SGD launch, one EMA
 launch, one gradient all-reduce).  The only host synchronisation per step is the
 read-back of ~60 list lengths that bound the reference's CPU ``torch.randint``
-anchor / negative sampling (kept for bit-identical sampling).
+anchor / negative sampling (kept for bit-identical sampling).  On one rank
+that read sits at the END of the step: the device applies the bounds to raw
+generator words the host uploaded ahead (``u2pl_infonce_plan``), so backward,
+SGD and EMA are enqueued before the host waits (``hipops.settle_host_reads``).
 
 Reference behaviours reproduced on purpose: label_onehot
 batch-slot-0 quirk (Q0), class-index mismatch (Q1), bank update before
@@ -203,6 +206,7 @@ class SemiTrainer:
         return [enc] + aux + [dec]
 
     def optimizer_state_dict(self):
+        H.settle_host_reads()
         m = self.lr_mult
         lrs = getattr(self, "last_lrs", None) or [self.base_lr * k for k in m]    # before the first step: the base lrs
         ref_lrs = [lrs[0]] + ([lrs[2]] if len(m) > 2 else []) + [lrs[1]]            # reference group order: encoder, aux, decoder
@@ -281,6 +285,7 @@ class SemiTrainer:
     def train_step(self, image_l, label_l, image_u, epoch, cutmix_boxes=None, randint=None, debug=None):
         cfg = self.cfg
         model, teacher = self.model, self.teacher
+        H.settle_host_reads()       # (a read the previous step deferred and an exception kept it from completing)
         if K._lib.SIDE_WORK:
             # an exception that escaped the previous step between a ledger entry and its removal (a caller may catch it and
             # go on): join what the entries stand for and clear them, instead of leaving every later split on the
@@ -414,14 +419,20 @@ class SemiTrainer:
             if ccfg:
                 _, contra_local = LH.contra_memobank_core(
                     rep_all, lbits, B, prob_all_t[:B], prob_all_t[B:], low_mask, high_mask, ccfg, self.memobank,
-                    rep_all_t, randint=randint)
-                H.check_split(rs)     # (the contrastive block just synchronised with the host: this read is free)
+                    rep_all_t, randint=randint, defer=True)
+                if H.host_read_pending():
+                    # the sampling was planned on the device: the step's one blocking read -- and with it this one -- waits
+                    # until backward, SGD and EMA are enqueued (the end of this function, or an earlier reader of host state)
+                    H.defer_check_split(rs)
+                else:
+                    H.check_split(rs)     # (the contrastive block just synchronised with the host: this read is free)
                 # Q5: value = cross-rank mean, gradient = local / world
                 contra_loss = contra_local * (float(ccfg.get("loss_weight", 1)) / _world())
             else:
                 H.watch_split(rs)     # no host sync on this path: the error word is examined one step later (non-blocking)
                 contra_loss = H.zero_times_sum(rep_all)
         if debug is not None and epoch >= self.sup_only_epoch:
+            H.settle_host_reads()            # (a caller that asks for the step's intermediates reads host state next)
             debug.update(label_u=label_u_aug, target_u=target_u, entropy=ent, thr=thr, pred_u_large=pred_u_large.detach())
             if ccfg:
                 debug.update(low_mask=low_mask, high_mask=high_mask, lbits=lbits)
@@ -446,6 +457,9 @@ class SemiTrainer:
             meters[2] = cv
             K._all_reduce(meters, "meter_allreduce")    # logged meters are cross-rank SUMS (train_semi.py:551-561)
             K.check_comm_sequence()     # (U2PL_COMM_DEBUG=1: every rank issued the same collectives in the same order)
+        # the step's one blocking read, with the whole step enqueued behind the kernels it waits for: list lengths -> bank
+        # bookkeeping, LAST_STATS, the CPU generator advanced by the draws the device applied, the split's error word
+        H.settle_host_reads()
         return meters
 
 

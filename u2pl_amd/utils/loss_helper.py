@@ -57,9 +57,54 @@ def _prob_layout(prob_l, prob_u):
     return prob, (C * h * w, h * w, 1)
 
 
+# Single rank, <= 32 classes, device-resident bank, default randint: the sampling of phase 2 is planned on the device
+# (u2pl_infonce_plan) from raw generator words the host uploads BEFORE it knows the list lengths, and the step's one
+# blocking read moves behind everything the step enqueues (settle_sampling; callers that pass defer=True promise to
+# call it -- the trainer does at the end of train_step).  U2PL_DEVICE_SAMPLING=0 keeps the read where the reference's
+# host draws need it; both give the same bits (tests/test_gpu_device_sampling.py).
+DEVICE_SAMPLING = os.environ.get("U2PL_DEVICE_SAMPLING", "1") != "0"
+
+
+def settle_sampling():
+    """complete a deferred read of the list lengths: bank bookkeeping, LAST_STATS, the generator (H.settle_host_reads)"""
+    H.settle_host_reads()
+
+
+def _contra_device_sampling(rep, rep_rows, rep_t_rows, D, ph1, memobank, cfg, C):
+    """phase-1 outputs -> key enqueue, sampling plan and InfoNCE forward, all from device-side lengths; the host's share
+    (mirror_counts, LAST_STATS, generator advance) is deferred to settle_sampling()"""
+    from .utils import BLOCKED_S
+    import time
+    Q, Kn = int(cfg["num_queries"]), int(cfg["num_negatives"])
+    with torch.no_grad():
+        memobank.enqueue_device(rep_t_rows, D, ph1.idx[2], ph1.cap, ph1.counts[2])
+    loss, plan = H.infonce_loss_device(rep_rows, ph1, memobank, cfg)
+    replay = H.REPLAY
+
+    def settle():
+        t0 = time.perf_counter()
+        try:
+            counts, njobs, valid_seg = H.plan_mirror(plan)
+        finally:
+            BLOCKED_S[0] += time.perf_counter() - t0
+        ph1.finish(counts)
+        memobank.mirror_counts(counts[2])
+        LAST_STATS.update(n_keys=int(sum(int(counts[2][c]) for c in range(C))), valid_seg=valid_seg, njobs=njobs, Q=Q, K=Kn)
+        H.infonce_loss.last_njobs = njobs
+        from .. import rng_words as RW
+        RW.advance(njobs * plan["per"])          # the draws the plan applied: njobs * (Q + Q K) words
+        if replay is not None and njobs > 0:
+            replay["infonce"] = (rep_rows.detach(), plan["jobs"], njobs, Q, Kn, float(cfg["temperature"]), valid_seg,
+                                 plan["groups"], (plan, ph1, memobank))
+    H.defer_host_read(settle)
+    return loss
+
+
 def contra_memobank_core(rep, lbits, num_labeled, prob_l, prob_u, low_mask, high_mask, cfg, memobank,
-                         rep_teacher, randint=None):
-    """Shared body; `lbits` = per-pixel class bitmask of the (quirky) multi-hot labels."""
+                         rep_teacher, randint=None, defer=False):
+    """Shared body; `lbits` = per-pixel class bitmask of the (quirky) multi-hot labels.
+    defer=True: the caller will call settle_sampling() once the rest of its step is enqueued, so the device-sampling path
+    may be taken (new_keys is None then: the lengths are not on the host yet; H.host_read_pending() tells)."""
     C = prob_l.shape[1]
     N2, D, h, w = rep.shape
     rep_rows = _rows_view(rep)
@@ -69,7 +114,12 @@ def contra_memobank_core(rep, lbits, num_labeled, prob_l, prob_u, low_mask, high
         ph1 = H.contra_phase1(rep_t_rows, D, D, prob, pstr, lbits, low_mask.contiguous(), high_mask.contiguous(),
                               num_labeled, C, h, w, cfg)
         from .. import nn as K      # (late: nn imports nothing from here, but keep the module graph acyclic at import time)
-        device_enqueue = not K.dist_active() and rep.is_cuda and isinstance(memobank, H.DeviceMemoryBank) and DEVICE_ENQUEUE
+        single_device_bank = not K.dist_active() and rep.is_cuda and isinstance(memobank, H.DeviceMemoryBank)
+    if (defer and DEVICE_SAMPLING and single_device_bank and randint is None and not ph1.wide
+            and H.sampling_device_ok(rep_rows, ph1, memobank, cfg)):
+        return None, _contra_device_sampling(rep, rep_rows, rep_t_rows, D, ph1, memobank, cfg, C)
+    with torch.no_grad():
+        device_enqueue = single_device_bank and DEVICE_ENQUEUE
         if device_enqueue and not ph1.wide:
             # single rank: the keys are appended by the device-resident bank from the list lengths ON THE DEVICE, i.e.
             # before (and under) the host synchronisation below instead of after it
