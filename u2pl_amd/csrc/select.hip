@@ -13,6 +13,15 @@
 //   [128 ..)            hist0[2048]
 //   [128+2048 ..)       hist1[8 slots][2048]
 //   [128+9*2048 ..)     hist2[8 slots][1024]
+//
+// NaN contract.  n_valid (word 0) counts the values that are not NaN, and a percentile's ranks run over those alone, so a NaN
+// must sort ABOVE every other value.  f32_key does that only for a NaN with a clear sign bit; one with the sign bit set
+// (0xffc00000 is what x86 gives for inf - inf) gets a key below -inf, would sit at rank 0 and shift every percentile.
+//   - The plain-array entry (hist0_done == 0) sorts EVERY NaN, of any sign and payload, above +inf: the passes below form
+//     their key with sel_key, which gives every NaN the key of 0x7fc00000.  A selected NaN is reported as 0x7fc00000.
+//   - A producer that hands over its own hist0 (hist0_done != 0) must write 0x7fc00000 on invalid pixels, as all of today's
+//     do: its histogram was built with f32_key, and passes 1 and 2 agree with it on that bit pattern only.
+// For every value that is not NaN, sel_key is f32_key (common.h, shared with the producers and relfused.hip).
 #include "common.h"
 #include "u2pl_hip.h"
 
@@ -26,6 +35,11 @@
 #define MAXS U2PL_SEL_MAX_SLOTS
 
 U2PL_API size_t u2pl_select_workspace_bytes(void) { return (size_t)SEL_WORDS * sizeof(unsigned); }
+
+__device__ __forceinline__ unsigned sel_key(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x7fffffffu) > 0x7f800000u ? 0xffc00000u : f32_key(f);
+}
 
 struct SelState {            // lives in LDS
     unsigned rank[MAXS];     // remaining rank inside the current prefix
@@ -160,11 +174,11 @@ __global__ void k_sel_hist0(const float* __restrict__ v, long n, unsigned* __res
     const long n4 = ((reinterpret_cast<uintptr_t>(v) & 15) == 0) ? (n >> 2) : 0;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const float4 x = ((const float4*)v)[i];
-        atomicAdd(&sh[f32_key(x.x) >> 21], 1u); atomicAdd(&sh[f32_key(x.y) >> 21], 1u);
-        atomicAdd(&sh[f32_key(x.z) >> 21], 1u); atomicAdd(&sh[f32_key(x.w) >> 21], 1u);
+        atomicAdd(&sh[sel_key(x.x) >> 21], 1u); atomicAdd(&sh[sel_key(x.y) >> 21], 1u);
+        atomicAdd(&sh[sel_key(x.z) >> 21], 1u); atomicAdd(&sh[sel_key(x.w) >> 21], 1u);
     }
     for (long i = 4 * n4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        atomicAdd(&sh[f32_key(v[i]) >> 21], 1u);
+        atomicAdd(&sh[sel_key(v[i]) >> 21], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < 2048; i += blockDim.x)
         if (sh[i]) atomicAdd(&ws[SEL_H0 + i], sh[i]);
@@ -201,7 +215,7 @@ __global__ void k_sel_pass(const float* __restrict__ v, long n, int nspec, const
         for (int j = 0; j < GROUP; ++j) pf[j] = j < cnt ? (S.prefix[lead[base + j]] >> SHIFT) : 0xffffffffu;
         __syncthreads();
         auto put = [&](float f) {
-            const unsigned k = f32_key(f);
+            const unsigned k = sel_key(f);
             const unsigned hi = k >> SHIFT;
             const unsigned d = PASS == 1 ? ((k >> 10) & 2047u) : (k & 1023u);
 #pragma unroll
