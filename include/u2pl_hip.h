@@ -850,6 +850,59 @@ int u2pl_bank_enqueue_wide_f32(long long* state, float* storage, int D, const fl
                                const long long* list_off_dev, const long long* row_start_dev,
                                const unsigned* counts_dev, int C, hipStream_t stream);
 
+/* ---- lovasz.hip -------------------------------------- */
+/* Segmented stable radix sort of (key, payload) uint32 pairs: segment s occupies elements [s * n, s * n + len_s) of keys /
+ * vals, len_s = seg_len_dev[s] clamped to [0, n] (seg_len_dev == NULL: every segment holds n).  Ascending on the low `bits`
+ * bits of the key (higher bits are carried along and ignored), equal keys keep their input order.  Least significant digit
+ * first, 8-bit digits, u2pl_segsort_passes(bits) = ceil(bits / 8) passes of histogram -> scan -> scatter between the two
+ * buffer pairs: after an even number of passes the result stands in keys / vals, after an odd number in keys_alt /
+ * vals_alt; the other pair holds the previous pass.  Elements past len_s are neither read nor written.  A wave orders a tile
+ * of u2pl_segsort_tile() elements; no block waits on another (the prefix over the tiles is a launch of its own), no atomics.
+ * ws: u2pl_segsort_ws_bytes(nseg, n) bytes, contents on entry do not matter.
+ * A null pointer, nseg outside [1, 65535], n outside [1, 2^31), bits outside [1, 32]: 1001 (ws_bytes and passes: 0). */
+int u2pl_segsort_passes(int bits);
+int u2pl_segsort_tile(void);
+size_t u2pl_segsort_ws_bytes(int nseg, long n);
+int u2pl_segsort_u32(unsigned* keys, unsigned* vals, unsigned* keys_alt, unsigned* vals_alt, void* ws, int nseg, long n,
+                     const int* seg_len_dev, int bits, hipStream_t stream);
+/* Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018, Algorithm 1 on the softmax errors) over the flattened batch:
+ * logits [N][C][H][W], target int64 [N][H][W], P = N H W pixels, pixels with target == ignore take no part.
+ *   m_i(c) = |[y_i == c] - softmax(z_i)[c]|; the valid pixels of class c sorted by m descending, ties in ascending pixel
+ *   index; F_j = foreground among the first j, G = foreground of the class, I_j = G - F_j, U_j = G + (j - F_j);
+ *   g_j = 1 / U_j (foreground), I_j / ((U_j - 1) U_j) (background, G > 0), [j == 1] (G == 0), formed in double;
+ *   loss_c = sum_j m_j g_j, loss = mean of loss_c over the classes with G > 0 (present_only) or over all C classes.
+ * Classes are processed in chunks of class_chunk (clamped to C; u2pl_lovasz_default_chunk() = 32, one chunk for Cityscapes);
+ * for each chunk start c0 = 0, cap, 2 cap, ... call errors -> sort -> grad, then finish once, all with the same ws and
+ * class_chunk.  ws: u2pl_lovasz_workspace_bytes(P, C, class_chunk) bytes, contents on entry do not matter.
+ *   errors  keys (0x3F800000 - bits(m); 0x3FFFFFFF on ignored pixels) and payloads (pixel | foreground << 31) of the chunk
+ *           [cc][P], the counts G[c] of its classes and the valid count
+ *   sort    u2pl_segsort_u32 on those buffers, 30 bits; the sorted order stands where errors wrote
+ *   grad    gplane[c][pixel] = g at the pixel's position (0 on ignored pixels and, with present_only, on absent classes) for
+ *           the classes of the chunk; every slot written once; fp32 slabs of m g per (class, tile)
+ *   finish  out3 = {loss, 1 / n_classes (0 when none), n_classes}; slabs added in double in a fixed order
+ *   bwd     grad[n][c][q] = p_c (a_c - sum_k a_k p_k), a_c = -/+ gplane[c][i] out3[1] gout gmul (minus where c == y_i); 0 on
+ *           ignored pixels.  gout_dev may be NULL (1).
+ * No atomics, no host read, the same bits on every run.  plan (host only): out[20] = {chunks, classes per chunk, tile,
+ * tiles per segment, errors blocks, count-reduction blocks, sort passes, sort / gradient grid.x, sort row-scan blocks,
+ * gradient row-scan blocks, byte offsets in ws of keys, payloads, alternate keys, alternate payloads, sort workspace,
+ * tile foreground counts, count partials, counts uint32 [C + 1] (G per class, then the valid count), slabs float
+ * [C][tiles], total bytes}.
+ * C outside [2, 255], P outside [1, 2^31), class_chunk < 1, a null required pointer, c0 not a chunk start: 1001 before any
+ * HIP call (workspace_bytes: 0). */
+size_t u2pl_lovasz_workspace_bytes(long P, int C, int class_chunk);
+int u2pl_lovasz_default_chunk(void);
+int u2pl_lovasz_plan(long P, int C, int class_chunk, long long* out);
+int u2pl_lovasz_errors_f32(const float* logits_nchw, const long long* target, int ignore, int N, int C, int H, int W,
+                           int c0, void* ws, int class_chunk, hipStream_t stream);
+int u2pl_lovasz_sort(long P, int C, int c0, void* ws, int class_chunk, hipStream_t stream);
+int u2pl_lovasz_grad_f32(long P, int C, int c0, int present_only, void* ws, int class_chunk, float* gplane,
+                         hipStream_t stream);
+int u2pl_lovasz_finish_f32(long P, int C, int present_only, const void* ws, int class_chunk, float* out3,
+                           hipStream_t stream);
+int u2pl_lovasz_bwd_f32(const float* logits_nchw, const long long* target, int ignore, int N, int C, int H, int W,
+                        const float* gplane, const float* out3_dev, const float* gout_dev, float gmul, float* grad,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

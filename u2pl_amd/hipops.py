@@ -588,6 +588,74 @@ def cross_entropy(logits, target, ignore_index=255, unsup_weight=False, scale=1.
     return _CrossEntropy.apply(logits, target, int(ignore_index), bool(unsup_weight), float(scale), class_weight)
 
 
+# --------------------------------------------------------------------------- Lovasz-Softmax (csrc/lovasz.hip)
+LOVASZ_CLASSES = ("present", "all")
+LOVASZ_PLAN_FIELDS = ("chunks", "cap", "tile", "tiles", "err_blocks", "count_blocks", "passes", "grid_x", "sort_scan_blocks",
+                      "grad_scan_blocks", "keys", "vals", "keys_alt", "vals_alt", "sort_ws", "tilefg", "part", "counts", "slabs",
+                      "total")
+
+
+def lovasz_plan(P, C, class_chunk=None):
+    """u2pl_lovasz_plan as a dict (host arithmetic only, no GPU): chunk count, tiles and grids per stage, workspace offsets"""
+    import ctypes
+    chunk = int(query("u2pl_lovasz_default_chunk") if class_chunk is None else class_chunk)
+    out = (ctypes.c_longlong * len(LOVASZ_PLAN_FIELDS))()
+    rc = query("u2pl_lovasz_plan", int(P), int(C), chunk, out)
+    if rc != 0:
+        raise _lib.HipError(f"u2pl_lovasz_plan({P}, {C}, {chunk}) failed with code {rc}")
+    return dict(zip(LOVASZ_PLAN_FIELDS, (int(v) for v in out)), class_chunk=chunk)
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """owns the workspace and the [C][P] plane of Lovasz gradients; fixed sizes, no host read: capturable by graphs.py"""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore, present_only, gmul, class_chunk):
+        _chk_cuda(logits, target)
+        x = _f32c(logits).contiguous()
+        N, C, H, W = x.shape
+        P = N * H * W
+        plan = lovasz_plan(P, C, class_chunk)
+        chunk = plan["class_chunk"]
+        work = torch.empty(plan["total"], dtype=torch.uint8, device=x.device)
+        gplane = torch.empty((C, P), dtype=torch.float32, device=x.device)
+        out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+        for c0 in range(0, C, plan["cap"]):
+            call("u2pl_lovasz_errors_f32", x, target, ignore, N, C, H, W, c0, work, chunk)
+            call("u2pl_lovasz_sort", P, C, c0, work, chunk)
+            call("u2pl_lovasz_grad_f32", P, C, c0, int(present_only), work, chunk, gplane)
+        call("u2pl_lovasz_finish_f32", P, C, int(present_only), work, chunk, out3)
+        ctx.save_for_backward(x, target, out3, gplane)
+        ctx.ignore, ctx.gmul = ignore, gmul
+        return out3[0].clone() * gmul if gmul != 1.0 else out3[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, target, out3, gplane = ctx.saved_tensors
+        N, C, H, W = x.shape
+        grad = torch.empty_like(x)
+        call("u2pl_lovasz_bwd_f32", x, target, ctx.ignore, N, C, H, W, gplane, out3, g.contiguous(), float(ctx.gmul), grad)
+        return grad, None, None, None, None, None
+
+
+def lovasz_softmax(logits, target, ignore_index=255, classes="present", scale=1.0, per_image=False, class_chunk=None):
+    """Lovasz-Softmax loss of the flattened batch (Berman et al. 2018) * scale; classes: "present" (classes with a labelled
+    pixel; 0 when there are none) or "all".  No per-image mode, no class list, no class weights.
+    class_chunk: classes sorted at a time (default u2pl_lovasz_default_chunk() = 32); bounds the workspace, not the result."""
+    if per_image:
+        raise ValueError("lovasz_softmax: per_image=True is not supported (the batch is flattened)")
+    if not isinstance(classes, str) or classes not in LOVASZ_CLASSES:
+        raise ValueError(f"lovasz_softmax: classes must be 'present' or 'all', got {classes!r} (class lists are not supported)")
+    if logits.dim() != 4 or not 2 <= logits.shape[1] <= WIDE_MAXC:
+        raise ValueError(f"lovasz_softmax: logits [N, C, H, W] with 2 <= C <= {WIDE_MAXC} expected, got {tuple(logits.shape)}")
+    if class_chunk is not None and int(class_chunk) < 1:
+        raise ValueError(f"lovasz_softmax: class_chunk = {class_chunk}: expected a positive chunk size")
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        target = target.long().contiguous()
+    return _LovaszSoftmax.apply(logits, target, int(ignore_index), classes == "present", float(scale),
+                                None if class_chunk is None else int(class_chunk))
+
+
 def ohem_kept_target(pred, target, thresh, min_kept, ignore_index=255):
     """OhemCrossEntropy2dTensor target rewrite (loss_helper.py:502-529), no host sync."""
     x = _f32c(pred.detach()).contiguous()

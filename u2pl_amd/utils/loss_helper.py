@@ -238,6 +238,44 @@ class Criterion(nn.Module, _AuxMixin):
         return loss
 
 
+class CriterionLovasz(nn.Module, _AuxMixin):
+    """ce_weight * CE + lovasz_weight * Lovasz-Softmax (Berman et al. 2018, H.lovasz_softmax) on the main head, plain CE times
+    aux_weight on the aux head.  Not in the reference.  The batch is flattened (no per-image mode), the errors are the softmax
+    ones (no hinge), no class weights, no OHEM; a weight of 0 makes no call for that term.  The loss is this rank's: it adds no
+    collective, so a multi-rank step (U2PL_DIST_SINGLE included) is refused by name."""
+
+    def __init__(self, aux_weight, ignore_index=255, ce_weight=1.0, lovasz_weight=1.0, classes="present", per_image=False,
+                 use_weight=False, class_chunk=None):
+        super().__init__()
+        if per_image:
+            raise ValueError("criterion lovasz: per_image=True is not supported (the batch is flattened)")
+        if use_weight:
+            raise ValueError("criterion lovasz: use_weight (class weights) is not supported")
+        if not isinstance(classes, str) or classes not in H.LOVASZ_CLASSES:
+            raise ValueError(f"criterion lovasz: classes must be 'present' or 'all', got {classes!r}")
+        if float(ce_weight) == 0.0 and float(lovasz_weight) == 0.0:
+            raise ValueError("criterion lovasz: ce_weight and lovasz_weight are both 0")
+        self._aux_weight, self._ignore_index = aux_weight, ignore_index
+        self.ce_weight, self.lovasz_weight, self.classes = float(ce_weight), float(lovasz_weight), classes
+        self.class_chunk = class_chunk
+
+    def forward(self, preds, target):
+        from ..comm import dist_active
+        if dist_active():
+            raise NotImplementedError("criterion lovasz: not supported on more than one rank or under U2PL_DIST_SINGLE")
+        main, aux = self._split(preds, target)
+        loss = None
+        if self.ce_weight != 0.0:
+            loss = H.cross_entropy(main, target, self._ignore_index, scale=self.ce_weight)
+        if self.lovasz_weight != 0.0:
+            lov = H.lovasz_softmax(main, target, self._ignore_index, classes=self.classes, scale=self.lovasz_weight,
+                                   class_chunk=self.class_chunk)
+            loss = lov if loss is None else loss + lov
+        if aux is not None:
+            loss = loss + H.cross_entropy(aux, target, self._ignore_index, scale=self._aux_weight)
+        return loss
+
+
 def get_criterion(cfg):
     cfg_criterion = cfg["criterion"]
     aux_weight = cfg["net"]["aux_loss"]["loss_weight"] if cfg["net"].get("aux_loss", False) else 0
@@ -245,4 +283,6 @@ def get_criterion(cfg):
     kw = cfg_criterion.get("kwargs", {}) or {}
     if cfg_criterion["type"] == "ohem":
         return CriterionOhem(aux_weight, ignore_index=ignore_index, **kw)
+    if cfg_criterion["type"] == "lovasz":
+        return CriterionLovasz(aux_weight, ignore_index=ignore_index, **kw)
     return Criterion(aux_weight, ignore_index=ignore_index, **kw)
