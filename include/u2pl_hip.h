@@ -645,6 +645,39 @@ size_t u2pl_region_attn_bwd_ws_floats(int N, int HW, int K, int D);
 int u2pl_region_attn_bwd_f32(const float* g_y, long ldg, const float* w, long ldw, const float* q, long ldq, const float* kk,
                              long ldk, const float* v, long ldv, float scale, int N, int HW, int K, int D, float* dq, long lddq,
                              float* dk, long lddk, float* dv, long lddv, float* ws, hipStream_t stream);
+/* Criss-cross attention (csrc/ccattn.hip; CCNet, Huang et al. 2019).  Every pixel p = (y, x) of an image
+   attends to its cross X(p): the W pixels of its row and the H - 1 other pixels of its column, L = H + W - 1 members.  All
+   maps are NHWC rows: q, k, dq, dk [N*H*W][D]; v, res, out, g, dv [N*H*W][C]; pitch a multiple of 4 and >= the row width, base
+   16-byte aligned (float4 accesses).  w is [N*H*W][L], single floats, any pitch >= L.  SLOT LAYOUT of w: for the pixel (y, x),
+   slot j < W is the row member (y, j) (the pixel itself is slot x) and slot W + i - (i > y) is the column member (i, x), i != y.
+   gamma is ONE float in device memory and is read on the device only (a graph replay sees the value SGD left there); scale is
+   a host float.
+   CONTRACT.  1001 before any launch, the outputs untouched, for: N, H or W < 1; D or C < 4 or not a multiple of 4;
+   H + W - 1 > 512 (CC_MAX_L: the map is too large for one cross; tiling a cross is out of scope); N*H*W >= 2^31; a null q, k,
+   v, gamma, w, out (forward) or g, w, gamma, ws (backward); a pitch below the row width, a channel-wide pitch that is not a
+   multiple of 4 or a base that is not 16-byte aligned; all of dq, dk, dv, dgamma null.  The backward reads k only for dq, q only
+   for dk and v only for dq, dk or dgamma: an operand that is not read may be null.
+   ARITHMETIC.  Exact fp32 on the vector ALU in a fixed order (first comment block of csrc/ccattn.hip), no atomics, no memset,
+   no U2PL_CONV_* switch applies: the same bits on every run, eager or replayed.  __fmaf_rn (one rounding): every step of a dot
+   product's chain over the channels, every step of a weighted sum's chain over the cross members, the lanes' chains of s[p],
+   and the forward's finish out = fma(gamma, sum, res).  Rounded apart: scale * dot, u - max, e / Z, the sums of Z, s and
+   dgamma, scale * gamma, (scale gamma) * w, t - s, their product, gamma * sum (no res; dv).
+   forward: w[p, m] = softmax over m in X(p) of scale * q[p] . k[m] (max-subtracted); out[p] = res[p] + gamma * sum_m w[p, m] v[m]
+   (res null: gamma * sum).  w and out are both written.  No workspace. */
+int u2pl_cc_attn_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* res,
+                         long ldr, const float* gamma, float scale, int N, int H, int W, int D, int C, float* w, long ldw,
+                         float* out, long ldo, hipStream_t stream);
+/* its backward, from g = d out and the saved w: t[p, m] = g[p] . v[m], s[p] = sum_m w t, e = scale gamma w (t - s);
+   dq[p] = sum_{m in X(p)} e[p, m] k[m]; dk[m] = sum_{p in X(m)} e[p, m] q[p] and dv[m] = gamma sum_{p in X(m)} w[p, m] g[p] (gathers
+   over the target's own cross with the weight the SOURCE p gives to m, each row written once); dgamma[0] = sum_{n, p} s[p] (one
+   float, written, not accumulated).  The gradient of res is g itself and is not this call's business.  Each of dq, dk, dv,
+   dgamma may be null (skipped), not all four.  ws: u2pl_cc_attn_bwd_ws_floats floats (0 for a shape out of contract), 16-byte
+   aligned; it holds t / e and the per-pixel s; its contents on entry do not matter. */
+size_t u2pl_cc_attn_bwd_ws_floats(int N, int H, int W, int D, int C);
+int u2pl_cc_attn_bwd_f32(const float* g, long ldg, const float* w, long ldw, const float* q, long ldq, const float* k, long ldk,
+                         const float* v, long ldv, const float* gamma, float scale, int N, int H, int W, int D, int C,
+                         float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, float* dgamma, float* ws,
+                         hipStream_t stream);
 /* torch.cat / slices (base.py:99, decoder.py:117), 1x1 -> HxW bilinear broadcast (base.py:92-94) */
 int u2pl_copy_rows_f32(const float* src, long lds, float* dst, long ldd, long M, int C, int accumulate,
                        hipStream_t stream);

@@ -1,6 +1,8 @@
 """DeepLabv3 / DeepLabv3+ decoders and the auxiliary head (reference: u2pl/models/decoder.py), a pyramid-pooling decoder
-(dec_pspnet) and an object-contextual one (dec_ocrnet).  nn.Sequential containers keep the reference's indices
-(``classifier.8.weight``); ReLU / Dropout2d entries are markers fused into the BatchNorm apply kernel by u2pl_amd.nn.run_seq."""
+(dec_pspnet), an object-contextual one (dec_ocrnet) and a criss-cross attention one (dec_ccnet).  nn.Sequential containers keep
+the reference's indices (``classifier.8.weight``); ReLU / Dropout2d entries are markers fused into the BatchNorm apply kernel by
+u2pl_amd.nn.run_seq."""
+import torch
 import torch.nn as nn
 
 from .. import nn as K
@@ -133,7 +135,7 @@ class dec_ocrnet(nn.Module):
     f_object(f), values f_down(f), one head: y = softmax_k(q . k / sqrt(key_planes)) v (K.region_attention); fuse: 1x1 over
     cat(f_up(y), pixel features) -> norm -> ReLU -> Dropout2d(0.05); classifier: 1x1 with bias.  rep_head: dec_pspnet's
     `representation` tower on the fused features.  Out of scope, refused or absent: more than 255 classes (regions), several
-    heads, pixel-to-pixel attention, a separable form, regions taken from the auxiliary head, OHEM on the region loss."""
+    heads, a separable form, regions taken from the auxiliary head, OHEM on the region loss.  (Pixel-to-pixel attention is dec_ccnet's.)"""
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=256, sync_bn=False, rep_head=False,
                  region_loss_weight=0.4):
@@ -179,6 +181,86 @@ class dec_ocrnet(nn.Module):
         y = K.run_seq(self.f_up, K.region_attention(q, kk, v, self.key_planes ** -0.5))
         out = K.run_seq(self.fuse, K.cat_channels((y, feat_p)))
         res = {"pred": self.classifier(out), "region": r}
+        if self.rep_head and need_rep:
+            res["rep"] = K.run_seq(self.representation, out)
+        return res
+
+
+class CrissCrossBlock(nn.Module):
+    """one criss-cross attention block (CCNet section 3.1): 1x1 query and key to key_planes, 1x1 value to planes, all with bias,
+    and gamma, one parameter that starts at 0: x + gamma * attention(x)"""
+
+    def __init__(self, planes, key_planes):
+        super().__init__()
+        self.query = K.Conv2d(planes, key_planes, kernel_size=1, stride=1, padding=0, bias=True)
+        self.key = K.Conv2d(planes, key_planes, kernel_size=1, stride=1, padding=0, bias=True)
+        self.value = K.Conv2d(planes, planes, kernel_size=1, stride=1, padding=0, bias=True)
+        self.gamma = nn.Parameter(torch.zeros(1))
+
+    def forward(self, x):
+        return K.criss_cross_attention(self.query(x), self.key(x), self.value(x), self.gamma, res=x, scale=1.0)
+
+
+class dec_ccnet(nn.Module):
+    """Criss-cross attention head (CCNet, Huang et al., ICCV 2019, section 3; no reference line: the reference has the two ASPP
+    heads only).  conva: 3x3 to inner_planes -> norm -> ReLU; cca: a CrissCrossBlock applied `recurrence` times (every pixel
+    attends to its own row and column, K.criss_cross_attention; two rounds give every pixel a path to every other); with
+    shared=False a ModuleList of `recurrence` blocks; convb: 3x3 -> norm -> ReLU; bottleneck: 3x3 over cat(input, convb) -> norm
+    -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: dec_pspnet's `representation` tower on the bottleneck.
+    A map with H + W - 1 > K.CC_MAX_L is refused (predict large images in sliding windows).  With shared=True and
+    recurrence > 1 the block's gradient sinks are written once per round, which the bucketed all-reduce does not count: that
+    combination is refused under a process group.  Out of scope, refused or absent: dense (non-local) self-attention, several
+    heads, a fused q/k/v projection, a tiled cross, the fp16 prediction path, a separable form."""
+
+    def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=64, recurrence=2, shared=True, sync_bn=False,
+                 rep_head=False):
+        super().__init__()
+        for name, val in (("in_planes", in_planes), ("inner_planes", inner_planes), ("key_planes", key_planes)):
+            if int(val) < 4 or int(val) % 4:
+                raise ValueError("dec_ccnet: %s (%r) must be a positive multiple of 4 (float4 rows)" % (name, val))
+        if int(recurrence) < 1:
+            raise ValueError("dec_ccnet: recurrence must be >= 1, got %r" % (recurrence,))
+        if not 2 <= int(num_classes) <= K.REGION_MAX_K:
+            raise ValueError("dec_ccnet: 2 <= num_classes <= %d (what the loss path takes), got %r" % (K.REGION_MAX_K, num_classes))
+        norm_layer = norm_layer_for(sync_bn)
+        self.rep_head, self.recurrence, self.shared = rep_head, int(recurrence), bool(shared)
+
+        def unit3x3(cin, cout, *tail):
+            return nn.Sequential(K.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, dilation=1, bias=False), norm_layer(cout),
+                                 nn.ReLU(inplace=True), *tail)
+
+        self.conva = unit3x3(in_planes, inner_planes)
+        if self.shared:
+            self.cca = CrissCrossBlock(inner_planes, key_planes)
+        else:
+            self.cca = nn.ModuleList(CrissCrossBlock(inner_planes, key_planes) for _ in range(self.recurrence))
+        self.convb = unit3x3(inner_planes, inner_planes)
+        self.bottleneck = unit3x3(in_planes + inner_planes, inner_planes, nn.Dropout2d(0.1))
+        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        if rep_head:
+            self.representation = nn.Sequential(
+                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
+                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
+                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+
+    def check_ranks(self):
+        """shared weights collect one gradient per round in the same sinks; the bucketed all-reduce counts one arrival per
+        parameter, so a process group would reduce a bucket before the second round's contribution"""
+        if self.shared and self.recurrence > 1 and K.dist_active():
+            raise NotImplementedError("dec_ccnet: shared attention weights over %d rounds are not supported on more than one rank or "
+                                      "under U2PL_DIST_SINGLE; `shared: false` or `recurrence: 1` run there" % self.recurrence)
+
+    def forward(self, x, need_rep=True):
+        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
+            x = x[-1]
+        if torch.is_grad_enabled():
+            self.check_ranks()
+        f = K.run_seq(self.conva, x)
+        for i in range(self.recurrence):
+            f = (self.cca if self.shared else self.cca[i])(f)
+        f = K.run_seq(self.convb, f)
+        out = K.run_seq(self.bottleneck, K.cat_channels((x, f)))
+        res = {"pred": self.classifier(out)}
         if self.rep_head and need_rep:
             res["rep"] = K.run_seq(self.representation, out)
         return res

@@ -1422,8 +1422,8 @@ def check_region_shapes(N, HW, K, C, what="region pool / attention"):
     pixels, K regions, C channels (the key width D of the attention)"""
     N, HW, K, C = int(N), int(HW), int(K), int(C)
     if not 1 <= K <= REGION_MAX_K:
-        raise ValueError("%s: 1 <= regions <= %d, got %d (more regions than that is pixel-to-pixel attention, which this "
-                         "project does not have)" % (what, REGION_MAX_K, K))
+        raise ValueError("%s: 1 <= regions <= %d, got %d (more regions than that is pixel-to-pixel attention: "
+                         "criss_cross_attention)" % (what, REGION_MAX_K, K))
     if C < 4 or C % 4:
         raise ValueError("%s: channels must be a positive multiple of 4 (float4 rows), got %d" % (what, C))
     if N < 1 or HW < 1 or N * HW >= 2 ** 31:
@@ -1521,6 +1521,85 @@ def region_attention(q, kk, v, scale):
     """-> y [N, D, H, W] = sum_k softmax_k(scale * q . kk[:, :, k]) v[:, :, k] for q [N, D, H, W] and keys / values
     [N, D, K, 1]: every pixel attends to the K regions of its own image (one head; K <= 255)."""
     return _RegionAttnFn.apply(q, kk, v, float(scale))
+
+
+CC_MAX_L = 512
+
+
+def check_cc_shapes(N, H, W, D, C, what="criss_cross_attention"):
+    """what the u2pl_cc_attn_* entry points (csrc/ccattn.hip) refuse with 1001, as a ValueError before any call: N images of
+    H x W pixels, D key channels, C value channels; a cross has L = H + W - 1 members"""
+    N, H, W, D, C = int(N), int(H), int(W), int(D), int(C)
+    if N < 1 or H < 1 or W < 1 or N * H * W >= 2 ** 31:
+        raise ValueError("%s: 1 <= N * H * W < 2^31, got %d x %d x %d" % (what, N, H, W))
+    if D < 4 or D % 4 or C < 4 or C % 4:
+        raise ValueError("%s: key and value channels must be positive multiples of 4 (float4 rows), got %d and %d" % (what, D, C))
+    if H + W - 1 > CC_MAX_L:
+        raise ValueError("%s: the %d x %d map is too large for one cross: H + W - 1 = %d members, the limit is %d (predict a "
+                         "large image in sliding windows)" % (what, H, W, H + W - 1, CC_MAX_L))
+    return N, H, W, D, C
+
+
+class _CrissCrossFn(torch.autograd.Function):
+    """out = res + gamma * sum over the cross of softmax(scale * q . k) v (csrc/ccattn.hip); saves q, k, v and the weights w.
+    gamma stays on the device (the step is replayed from a graph while SGD moves it); res's gradient is g itself.  dgamma is
+    returned to autograd as a 1-element tensor; a gamma that lives in a ParamArena gets it added into its gradient sink by
+    this backward instead, like every other parameter of the models (no accumulation node of autograd's inside a captured pass)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, gamma, res, scale):
+        qr, ldq = as_rows(q)
+        kr, ldk = as_rows(k)
+        vr, ldv = as_rows(v)
+        N, D, H, W = qr.shape
+        C = vr.shape[1]
+        if tuple(kr.shape) != (N, D, H, W) or tuple(vr.shape) != (N, C, H, W) or (res is not None and tuple(res.shape) != (N, C, H, W)):
+            raise ValueError("criss_cross_attention: q %r, k %r, v %r and res %r do not fit" % (
+                tuple(q.shape), tuple(k.shape), tuple(v.shape), None if res is None else tuple(res.shape)))
+        if gamma.numel() != 1 or gamma.dtype != torch.float32 or not gamma.is_cuda:
+            raise ValueError("criss_cross_attention: gamma must be one float32 on the device, got %r" % (tuple(gamma.shape),))
+        check_cc_shapes(N, H, W, D, C)
+        rr, ldr = (None, C) if res is None else as_rows(res)
+        L = H + W - 1
+        w = torch.empty((N * H * W, L), dtype=torch.float32, device=qr.device)
+        out = new_act(N, C, H, W, qr.device)
+        call("u2pl_cc_attn_fwd_f32", qr, ldq, kr, ldk, vr, ldv, rr, ldr, gamma, scale, N, H, W, D, C, w, L, out, C)
+        ctx.save_for_backward(qr, kr, vr, w, gamma)
+        ctx.meta = (N, D, C, H, W, ldq, ldk, ldv, scale)
+        ctx.gsink = _grad_sink(gamma)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        if g is None:
+            return None, None, None, None, None, None
+        dres = g if need[4] else None
+        if not any(need[:4]):
+            return None, None, None, None, dres, None
+        N, D, C, H, W, ldq, ldk, ldv, scale = ctx.meta
+        qr, kr, vr, w, gamma = ctx.saved_tensors
+        gr, ldg = as_rows(g)
+        dq = new_act(N, D, H, W, gr.device) if need[0] else None
+        dk = new_act(N, D, H, W, gr.device) if need[1] else None
+        dv = new_act(N, C, H, W, gr.device) if need[2] else None
+        dgamma = torch.empty(gamma.shape, dtype=torch.float32, device=gr.device) if need[3] else None
+        ws = _f32_ws(query("u2pl_cc_attn_bwd_ws_floats", N, H, W, D, C), gr.device)
+        call("u2pl_cc_attn_bwd_f32", gr, ldg, w, H + W - 1, qr, ldq, kr, ldk, vr, ldv, gamma, scale, N, H, W, D, C, dq, D, dk, D,
+             dv, C, dgamma, ws)
+        if dgamma is not None and ctx.gsink is not None:
+            ctx.gsink.add_(dgamma.reshape(ctx.gsink.shape))      # (a shared block's gamma collects one term per round)
+            _mark_ready(ctx.gsink)
+            dgamma = None
+        return dq, dk, dv, dgamma, dres, None
+
+
+def criss_cross_attention(q, k, v, gamma, res=None, scale=1.0):
+    """-> out [N, C, H, W] = res + gamma * sum_{m in X(p)} softmax_m(scale * q[p] . k[m]) v[m] for q, k [N, D, H, W] and v, res
+    [N, C, H, W]: every pixel attends to the H + W - 1 pixels of its own row and column (one head; H + W - 1 <= CC_MAX_L).
+    gamma: one float32 on the device.  res None: the attention output alone."""
+    return _CrissCrossFn.apply(q, k, v, gamma, res, float(scale))
 
 
 class _BroadcastFn(torch.autograd.Function):
