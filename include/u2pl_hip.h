@@ -678,6 +678,34 @@ int u2pl_cc_attn_bwd_f32(const float* g, long ldg, const float* w, long ldw, con
                          const float* v, long ldv, const float* gamma, float scale, int N, int H, int W, int D, int C,
                          float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, float* dgamma, float* ws,
                          hipStream_t stream);
+/* Dense (non-local) attention, several heads (csrc/attn.hip; Non-local networks, Wang et al. 2018).  Per
+   image n and head h: S = scale q_h k_h^T ([Pq][Pk], never in memory), P = softmax over the keys, o_h = P v_h,
+   lse = max_j S + log sum_j exp(S - max) (natural log).  Rows: q, dq [N*Pq][heads*D]; k, dk [N*Pk][heads*D]; v, dv
+   [N*Pk][heads*Dv]; o, g [N*Pq][heads*Dv]; head h owns the columns h*D .. / h*Dv ..; pitch a multiple of 4 and >= the row
+   width, base 16-byte aligned (float4 accesses).  lse is dense: lse[(n*heads + h)*Pq + p].  scale is a host float.
+   CONTRACT.  1001 before any launch, the outputs untouched, for: N, heads, Pq or Pk < 1; D outside 4 .. 128 or not a multiple
+   of 4; Dv outside 4 .. 512 or not a multiple of 4; N*heads*Pq, N*Pq or N*Pk >= 2^31; a null q, k, v, o, lse (forward) or g, q,
+   k, lse, ws (backward); a pitch below the row width or not a multiple of 4, a base that is not 16-byte aligned; all of dq, dk,
+   dv null.  There is no cap on Pq or Pk.  The backward reads v and o only for dq or dk: with both null they may be null.
+   ARITHMETIC.  Exact fp32, the products on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), softmax, rescale and delta on the
+   vector ALU, in a fixed order that depends on the shapes alone (ARITHMETIC CONTRACT block of csrc/attn.hip): keys in tiles of
+   64 ascending with an online softmax (running maximum, one rescale of the sums per tile), one IEEE division at the end; no
+   atomics, no memset, no host read, fixed launch sizes: the same bits on every run, eager or replayed.  Nothing of size
+   Pq x Pk is written: the backward recomputes P = exp(S - lse).
+   forward: writes o and lse.  The workspace query is 0 for every shape; ws is not read and may be null. */
+size_t u2pl_attn_fwd_ws_floats(int N, int heads, int Pq, int Pk, int D, int Dv);
+int u2pl_attn_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float scale, int N, int heads,
+                      int Pq, int Pk, int D, int Dv, float* o, long ldo, float* lse, float* ws, hipStream_t stream);
+/* its backward, from g = d o and the forward's o and lse: delta[p, h] = g[p, h, :] . o[p, h, :], dP = g v^T,
+   dS = P o (dP - delta); dq = scale dS k; dk = scale dS^T q; dv = P^T g.  Each of dq, dk, dv may be null (skipped), not all
+   three.  dq comes from blocks that own 64 queries and walk the key tiles ascending; dk and dv from blocks that own 64 keys and
+   walk the query tiles ascending; with few key tiles the queries are cut into slabs whose partial sums are added in slab order.
+   ws: u2pl_attn_bwd_ws_floats floats (0 for a shape out of contract), 16-byte aligned; it holds delta and the slab partials
+   (O(rows x channels x slabs)); its contents on entry do not matter. */
+size_t u2pl_attn_bwd_ws_floats(int N, int heads, int Pq, int Pk, int D, int Dv);
+int u2pl_attn_bwd_f32(const float* g, long ldg, const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
+                      const float* o, long ldo, const float* lse, float scale, int N, int heads, int Pq, int Pk, int D, int Dv,
+                      float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, float* ws, hipStream_t stream);
 /* torch.cat / slices (base.py:99, decoder.py:117), 1x1 -> HxW bilinear broadcast (base.py:92-94) */
 int u2pl_copy_rows_f32(const float* src, long lds, float* dst, long ldd, long M, int C, int accumulate,
                        hipStream_t stream);

@@ -1,6 +1,6 @@
 """DeepLabv3 / DeepLabv3+ decoders and the auxiliary head (reference: u2pl/models/decoder.py), a pyramid-pooling decoder
-(dec_pspnet), an object-contextual one (dec_ocrnet) and a criss-cross attention one (dec_ccnet).  nn.Sequential containers keep
-the reference's indices (``classifier.8.weight``); ReLU / Dropout2d entries are markers fused into the BatchNorm apply kernel by
+(dec_pspnet), an object-contextual one (dec_ocrnet), a criss-cross attention one (dec_ccnet) and a dense (non-local) attention one
+(dec_nonlocal).  nn.Sequential containers keep the reference's indices (``classifier.8.weight``); ReLU / Dropout2d entries are markers fused into the BatchNorm apply kernel by
 u2pl_amd.nn.run_seq."""
 import torch
 import torch.nn as nn
@@ -209,8 +209,8 @@ class dec_ccnet(nn.Module):
     -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: dec_pspnet's `representation` tower on the bottleneck.
     A map with H + W - 1 > K.CC_MAX_L is refused (predict large images in sliding windows).  With shared=True and
     recurrence > 1 the block's gradient sinks are written once per round, which the bucketed all-reduce does not count: that
-    combination is refused under a process group.  Out of scope, refused or absent: dense (non-local) self-attention, several
-    heads, a fused q/k/v projection, a tiled cross, the fp16 prediction path, a separable form."""
+    combination is refused under a process group.  Out of scope, refused or absent: a fused q/k/v projection, a tiled cross,
+    the fp16 prediction path, a separable form.  (Dense attention and several heads are dec_nonlocal's.)"""
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=64, recurrence=2, shared=True, sync_bn=False,
                  rep_head=False):
@@ -259,6 +259,82 @@ class dec_ccnet(nn.Module):
         for i in range(self.recurrence):
             f = (self.cca if self.shared else self.cca[i])(f)
         f = K.run_seq(self.convb, f)
+        out = K.run_seq(self.bottleneck, K.cat_channels((x, f)))
+        res = {"pred": self.classifier(out)}
+        if self.rep_head and need_rep:
+            res["rep"] = K.run_seq(self.representation, out)
+        return res
+
+
+class NonLocalBlock(nn.Module):
+    """one dense self-attention block (Non-local networks, Wang et al., CVPR 2018, section 3.3, in its embedded-Gaussian form):
+    query: 1x1 planes -> key_planes; key: 1x1 planes -> key_planes and value: 1x1 planes -> value_planes, both with stride
+    kv_stride (1 or 2: the strided 1x1 of ResNet's downsample; with 2 the keys are the ceil(H/2) x ceil(W/2) sub-grid), all
+    three with bias; project: 1x1 value_planes -> planes without bias -> norm whose WEIGHT STARTS AT 0 (the paper's
+    initialisation: the block is the identity at step 0).  forward: x + project(K.dense_attention(q, k, v, heads, scale)); the
+    residual is the BatchNorm apply's own residual operand (the route of a bottleneck's tail)."""
+
+    def __init__(self, planes, key_planes, value_planes, heads=1, kv_stride=1, scale=None, norm_layer=K.BatchNorm2d):
+        super().__init__()
+        self.heads, self.scale = int(heads), scale
+        self.query = K.Conv2d(planes, key_planes, kernel_size=1, stride=1, padding=0, bias=True)
+        self.key = K.Conv2d(planes, key_planes, kernel_size=1, stride=kv_stride, padding=0, bias=True)
+        self.value = K.Conv2d(planes, value_planes, kernel_size=1, stride=kv_stride, padding=0, bias=True)
+        self.project = nn.Sequential(K.Conv2d(value_planes, planes, kernel_size=1, stride=1, padding=0, bias=False), norm_layer(planes))
+        nn.init.zeros_(self.project[1].weight)
+
+    def forward(self, x):
+        y = K.dense_attention(self.query(x), self.key(x), self.value(x), heads=self.heads, scale=self.scale)
+        return K.conv_bn(self.project[0], self.project[1], y, res=x)
+
+
+class dec_nonlocal(nn.Module):
+    """Non-local head (Wang et al., CVPR 2018; the position attention of DANet, Fu et al., CVPR 2019, is this block with
+    value_planes = inner_planes; no reference line: the reference has the two ASPP heads only), shaped as dec_ccnet with a
+    NonLocalBlock in the place of the criss-cross rounds.  conva: 3x3 to inner_planes -> norm -> ReLU; nl: every pixel attends
+    to every pixel (K.dense_attention, csrc/attn.hip: tiled, online softmax, nothing of size pixels x pixels stored, so no cap on
+    the map); convb: 3x3 -> norm -> ReLU; bottleneck: 3x3 over cat(input, convb) -> norm -> ReLU -> Dropout2d(0.1); classifier:
+    1x1 with bias.  rep_head: dec_pspnet's `representation` tower on the bottleneck.  key_planes / heads <= K.ATTN_MAX_D and
+    value_planes / heads <= K.ATTN_MAX_DV per head.  Out of scope, refused or absent: masks and causal attention, dropout on
+    the weights, relative position terms, a fused q/k/v projection, DANet's channel-attention branch, the fp16 prediction path."""
+
+    def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=64, value_planes=256, heads=1, kv_stride=1,
+                 scale=None, sync_bn=False, rep_head=False):
+        super().__init__()
+        for name, val in (("in_planes", in_planes), ("inner_planes", inner_planes), ("key_planes", key_planes),
+                          ("value_planes", value_planes)):
+            if int(val) < 4 or int(val) % 4:
+                raise ValueError("dec_nonlocal: %s (%r) must be a positive multiple of 4 (float4 rows)" % (name, val))
+        if int(heads) < 1 or int(key_planes) % int(heads) or int(value_planes) % int(heads):
+            raise ValueError("dec_nonlocal: key_planes (%r) and value_planes (%r) must divide into heads (%r)" % (
+                key_planes, value_planes, heads))
+        K.check_attn_shapes(1, heads, 1, 1, int(key_planes) // int(heads), int(value_planes) // int(heads), "dec_nonlocal")
+        if kv_stride not in (1, 2):
+            raise ValueError("dec_nonlocal: kv_stride must be 1 or 2, got %r" % (kv_stride,))
+        if not 2 <= int(num_classes) <= K.REGION_MAX_K:
+            raise ValueError("dec_nonlocal: 2 <= num_classes <= %d (what the loss path takes), got %r" % (K.REGION_MAX_K, num_classes))
+        norm_layer = norm_layer_for(sync_bn)
+        self.rep_head = rep_head
+
+        def unit3x3(cin, cout, *tail):
+            return nn.Sequential(K.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, dilation=1, bias=False), norm_layer(cout),
+                                 nn.ReLU(inplace=True), *tail)
+
+        self.conva = unit3x3(in_planes, inner_planes)
+        self.nl = NonLocalBlock(inner_planes, key_planes, value_planes, heads, kv_stride, scale, norm_layer)
+        self.convb = unit3x3(inner_planes, inner_planes)
+        self.bottleneck = unit3x3(in_planes + inner_planes, inner_planes, nn.Dropout2d(0.1))
+        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        if rep_head:
+            self.representation = nn.Sequential(
+                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
+                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
+                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+
+    def forward(self, x, need_rep=True):
+        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
+            x = x[-1]
+        f = K.run_seq(self.convb, self.nl(K.run_seq(self.conva, x)))
         out = K.run_seq(self.bottleneck, K.cat_channels((x, f)))
         res = {"pred": self.classifier(out)}
         if self.rep_head and need_rep:

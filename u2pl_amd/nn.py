@@ -1602,6 +1602,81 @@ def criss_cross_attention(q, k, v, gamma, res=None, scale=1.0):
     return _CrissCrossFn.apply(q, k, v, gamma, res, float(scale))
 
 
+ATTN_MAX_D = 128
+ATTN_MAX_DV = 512
+
+
+def check_attn_shapes(N, heads, Pq, Pk, D, Dv, what="dense_attention"):
+    """what the u2pl_attn_* entry points (csrc/attn.hip) refuse with 1001, as a ValueError before any call: N images, `heads`
+    heads, Pq queries and Pk keys per image, D key and Dv value channels PER HEAD"""
+    N, heads, Pq, Pk, D, Dv = int(N), int(heads), int(Pq), int(Pk), int(D), int(Dv)
+    if N < 1 or heads < 1 or Pq < 1 or Pk < 1:
+        raise ValueError("%s: N, heads, queries and keys must be >= 1, got %d, %d, %d, %d" % (what, N, heads, Pq, Pk))
+    if not 4 <= D <= ATTN_MAX_D or D % 4:
+        raise ValueError("%s: key channels per head must be a multiple of 4 in 4 .. %d, got %d" % (what, ATTN_MAX_D, D))
+    if not 4 <= Dv <= ATTN_MAX_DV or Dv % 4:
+        raise ValueError("%s: value channels per head must be a multiple of 4 in 4 .. %d, got %d" % (what, ATTN_MAX_DV, Dv))
+    if N * heads * Pq >= 2 ** 31 or N * Pq >= 2 ** 31 or N * Pk >= 2 ** 31:
+        raise ValueError("%s: N * heads * queries, N * queries and N * keys must be < 2^31, got %d x %d x %d / %d" % (
+            what, N, heads, Pq, Pk))
+    return N, heads, Pq, Pk, D, Dv
+
+
+class _DenseAttnFn(torch.autograd.Function):
+    """o = softmax over the keys of (scale * q_h . k_h) v_h per head (csrc/attn.hip); saves q, k, v, o and the row statistics lse:
+    the weights are never stored, the backward recomputes them.  An input that needs no gradient is a null output of the call."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        qr, ldq = as_rows(q)
+        kr, ldk = as_rows(k)
+        vr, ldv = as_rows(v)
+        N, QD, Hq, Wq = qr.shape
+        _, _, Hk, Wk = kr.shape
+        VD = vr.shape[1]
+        if kr.shape[0] != N or kr.shape[1] != QD or tuple(vr.shape) != (N, VD, Hk, Wk) or QD % heads or VD % heads:
+            raise ValueError("dense_attention: q %r, k %r, v %r and heads %r do not fit" % (
+                tuple(q.shape), tuple(k.shape), tuple(v.shape), heads))
+        D, Dv, Pq, Pk = QD // heads, VD // heads, Hq * Wq, Hk * Wk
+        check_attn_shapes(N, heads, Pq, Pk, D, Dv)
+        o = new_act(N, VD, Hq, Wq, qr.device)
+        lse = torch.empty(N * heads * Pq, dtype=torch.float32, device=qr.device)
+        ws = _f32_ws(query("u2pl_attn_fwd_ws_floats", N, heads, Pq, Pk, D, Dv), qr.device)
+        call("u2pl_attn_fwd_f32", qr, ldq, kr, ldk, vr, ldv, scale, N, heads, Pq, Pk, D, Dv, o, VD, lse, ws)
+        ctx.save_for_backward(qr, kr, vr, o, lse)
+        ctx.meta = (N, heads, Pq, Pk, D, Dv, ldq, ldk, ldv, scale, (Hq, Wq), (Hk, Wk))
+        ctx.set_materialize_grads(False)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        if g is None or not any(need[:3]):
+            return None, None, None, None, None
+        N, heads, Pq, Pk, D, Dv, ldq, ldk, ldv, scale, (Hq, Wq), (Hk, Wk) = ctx.meta
+        qr, kr, vr, o, lse = ctx.saved_tensors
+        gr, ldg = as_rows(g)
+        dq = new_act(N, heads * D, Hq, Wq, gr.device) if need[0] else None
+        dk = new_act(N, heads * D, Hk, Wk, gr.device) if need[1] else None
+        dv = new_act(N, heads * Dv, Hk, Wk, gr.device) if need[2] else None
+        ws = _f32_ws(query("u2pl_attn_bwd_ws_floats", N, heads, Pq, Pk, D, Dv), gr.device)
+        call("u2pl_attn_bwd_f32", gr, ldg, qr, ldq, kr, ldk, vr, ldv, o, heads * Dv, lse, scale, N, heads, Pq, Pk, D, Dv,
+             dq, heads * D, dk, heads * D, dv, heads * Dv, ws)
+        return dq, dk, dv, None, None
+
+
+def dense_attention(q, k, v, heads=1, scale=None):
+    """-> o [N, heads*Dv, Hq, Wq] = softmax_j(scale * q_h[p] . k_h[j]) v_h[j] per head for q [N, heads*D, Hq, Wq], k [N, heads*D, Hk, Wk]
+    and v [N, heads*Dv, Hk, Wk]: every query pixel attends to every key pixel (the key map may be smaller than the query map).
+    scale None: D ** -0.5.  D <= ATTN_MAX_D, Dv <= ATTN_MAX_DV per head; no cap on the map sizes."""
+    heads = int(heads)
+    if heads < 1 or q.shape[1] % heads:
+        raise ValueError("dense_attention: %d query channels do not divide into %r heads" % (q.shape[1], heads))
+    if scale is None:
+        scale = float(q.shape[1] // heads) ** -0.5
+    return _DenseAttnFn.apply(q, k, v, heads, float(scale))
+
+
 class _BroadcastFn(torch.autograd.Function):
     """bilinear(align_corners=True) up-sampling of a 1x1 map == broadcast (base.py:92-94)."""
 
