@@ -14,17 +14,30 @@ A block against its float64 twin: Bottleneck(256, 64, groups=32, base_width=4) i
 from F.conv2d / F.batch_norm / relu in float64; yardstick: the same test on the dense Bottleneck(256, 64); each grouped figure
 (max|got - ref| / max|ref| of the output, the input gradient and every parameter gradient) must be <= 2x the dense block's.
 
-The whole path: ResNeXt-50 32x4d + DeepLabv3+ through ModelBuilder at 65 x 65."""
+The whole path: ResNeXt-50 32x4d + DeepLabv3+ through ModelBuilder at 65 x 65.
+
+Every width, tap and pixel edge (the second half of this file): the table of tests/gconv_bounds.py -- Cin/groups != Cout/groups, three
+column tiles, partial last tiles, filters other than 3x3 and 1x1, Wout < 4, 5 to 34816 pixels -- through the three C entry points with
+the same oracle and bound (n = R*S*Cin/groups for y, R*S*Cout/groups for dx, N*Ho*Wo for dw).  x, dy, y and dx are channel slices
+of wider buffers: NaN beside the inputs, a sentinel around the outputs (the columns outside the slice, two rows in front, three rows
+past M, the tail of dw) and behind the workspace, which is allocated at exactly the queried size and filled with NaN.
+tests/test_gconv_cpu.py shows on an emulation that this bound on this table rejects seven one-line addressing mistakes that the
+table above cannot see.  Each case prints its excess (pytest -s); U2PL_GCONV_RECORD=path writes the largest |got - f64| / bound per
+entry point and kernel family as JSON (profiles/gconv_bounds.json is one such run: a record, not a threshold)."""
 import copy
+import functools
+import json
 import math
+import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import gconv_bounds as B
 from model_utils import net_cfg
-from split_bounds import EPS, excess, recorded_calls
+from split_bounds import EPS, conv_dx_bound, excess, recorded_calls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -370,3 +383,221 @@ def test_resnext_graph_replay_is_bit_identical_to_eager(monkeypatch):
     assert np.isfinite(a["meters"]).all()
     assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
     assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+
+
+# ---- every width, tap and pixel edge: the table of tests/gconv_bounds.py in sentinel frames -------------------------------------
+SENT = -7.25e22
+WORST = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _records():
+    yield
+    for key in sorted(WORST):
+        print("worst  %-40s %.4f" % (key, WORST[key]))
+    path = os.environ.get("U2PL_GCONV_RECORD")
+    if path:
+        with open(path, "w") as f:
+            json.dump({k: round(v, 4) for k, v in sorted(WORST.items())}, f, indent=1)
+            f.write("\n")
+
+
+class Frame:
+    """a [M][C] row tensor as a channel slice of a wider buffer: rows [front + M + back][C + extra] filled with `fill`, the slice
+    at column `off`.  ptr: what an entry point is handed; rows(): the slice; intact(): the frame has kept its bits"""
+
+    def __init__(self, M, C, extra, off, fill, front=2, back=3):
+        assert extra % 4 == 0 and off % 4 == 0 and off <= extra
+        self.M, self.C, self.ld = M, C, C + extra
+        self.start = front * self.ld + off
+        self.buf = torch.full(((front + M + back) * self.ld,), fill, device=DEV)
+        assert self.buf.data_ptr() % 16 == 0
+        self.ptr = self.buf[self.start:]
+        self.before = None
+
+    def rows(self):
+        return torch.as_strided(self.buf, (self.M, self.C), (self.ld, 1), self.start)
+
+    def arm(self):
+        self.before = self.buf.clone()
+        return self
+
+    def intact(self):
+        now = self.buf.clone()
+        self.rows().copy_(torch.as_strided(self.before, (self.M, self.C), (self.ld, 1), self.start))    # the slice put back: the rest is the frame
+        same = torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
+        self.buf.copy_(now)
+        return same
+
+
+def _to_rows(t):
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).to(DEV)
+
+
+def _from_rows(rows, N, H, W):
+    return rows.reshape(N, H, W, rows.shape[1]).permute(0, 3, 1, 2).cpu()
+
+
+def run_case(case, x, w, gy, bias=None, sink=None):
+    """the three C entry points on one case, every tensor in its frame -> y, dx, dw, dw2 (CPU, logical shapes)"""
+    from u2pl_amd import nn as K
+    groups, cig, cog, R, S, H, W, stride, pad, dil, N = case
+    Cin, Cout = groups * cig, groups * cog
+    Ho, Wo = B.out_hw(case)
+    My, Mx = N * Ho * Wo, N * H * W
+    nan = float("nan")
+    xf, gf = Frame(Mx, Cin, 24, 8, nan), Frame(My, Cout, 40, 12, nan)                   # NaN beside and behind the inputs
+    xf.rows().copy_(_to_rows(x))
+    gf.rows().copy_(_to_rows(gy))
+    yf, dxf = Frame(My, Cout, 12, 4, SENT).arm(), Frame(Mx, Cin, 20, 16, SENT).arm()
+    E = Cout * R * S * cig
+    wdv = w.permute(0, 2, 3, 1).contiguous().reshape(-1).to(DEV)                        # [Cout][R][S][cig]
+    bd = None if bias is None else bias.to(DEV)
+    geo = (N, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, groups)
+    K.call("u2pl_gconv2d_fwd_f32", xf.ptr, xf.ld, wdv, bd, yf.ptr, yf.ld, *geo)
+    K.call("u2pl_gconv2d_dgrad_f32", gf.ptr, gf.ld, wdv, dxf.ptr, dxf.ld, *geo)
+    nbytes = int(K.query("u2pl_gconv2d_wgrad_workspace_bytes", N, Ho, Wo, Cin, Cout, R, S, groups))
+    assert nbytes == B.workspace_bytes(case) and nbytes % 16 == 0
+    ws = torch.full((nbytes // 4 + 64,), nan, device=DEV)                               # exactly the queried size, then a sentinel tail
+    ws[nbytes // 4:] = SENT
+    dws = []
+    for _ in range(2):
+        dw = torch.full((E + 64,), SENT, device=DEV)
+        if sink is not None:
+            dw[:E] = sink.permute(0, 2, 3, 1).reshape(-1).to(DEV)
+        K.call("u2pl_gconv2d_wgrad_f32", gf.ptr, gf.ld, xf.ptr, xf.ld, dw, ws, int(sink is not None), *geo)
+        dws.append(dw)
+    torch.cuda.synchronize()
+    assert yf.intact(), "the forward wrote outside y"
+    assert dxf.intact(), "the data gradient wrote outside dx"
+    assert bool((ws[nbytes // 4:] == SENT).all()), "the weight gradient wrote past the queried workspace"
+    assert all(bool((d[E:] == SENT).all()) for d in dws), "the weight gradient wrote past dw"
+    dw, dw2 = (d[:E].reshape(Cout, R, S, cig).permute(0, 3, 1, 2).cpu() for d in dws)
+    return dict(y=_from_rows(yf.rows(), N, Ho, Wo), dx=_from_rows(dxf.rows(), N, H, W), dw=dw, dw2=dw2)
+
+
+def family(case):
+    """entry point and kernel template per output"""
+    return dict(y="fwd k_gconv<%d, false>" % B.col_tiles(case[2]), dx="dgrad k_gconv<%d, true>" % B.col_tiles(case[1]),
+                dw="wgrad k_gconv_wgrad<%d>" % B.wgrad_family(case[3] * case[4]))
+
+
+def held(case, got, refs, tag):
+    worst = B.worst(got, refs)
+    print("gconv", tag, {k: round(v, 4) for k, v in worst.items()})
+    for name, key in family(case).items():
+        WORST[key] = max(WORST.get(key, 0.0), worst[name])
+    assert all(v <= 1.0 for v in worst.values()), (tag, worst)
+    assert torch.equal(got["dw"].view(torch.int32), got["dw2"].view(torch.int32)), "the weight gradient must give the same bits twice"
+    for name in B.NAMES:                    # a bound of 0 (only padding is met, no bias, no sink): exactly 0
+        ref, bound = refs[name]
+        assert bool((got[name][bound == 0] == 0).all()), (tag, name)
+
+
+@functools.lru_cache(maxsize=None)
+def _case_data(case):
+    """operands and float64 references of one case: computed once, shared, not modified"""
+    ops = B.operands(case)
+    return ops, B.refs(case, *ops)
+
+
+TABLE = B.shape_list()
+
+
+@pytest.mark.parametrize("case", TABLE, ids=[B.case_id(c) for c in TABLE])
+def test_whole_table_in_sentinel_frames(case):
+    (x, w, gy), refs = _case_data(case)
+    got = run_case(case, x, w, gy)
+    held(case, got, refs, B.case_id(case))
+    for name in B.NAMES:                    # not vacuous: the outputs are there
+        assert float(got[name].abs().max()) > 0
+
+
+def test_bias_and_accumulate_on_a_5x5_with_unequal_widths():
+    """bias in the forward's epilogue; the weight gradient added into a sink as large as dw itself"""
+    case = (8, 4, 12, 5, 5, 13, 11, 1, 2, 1, 2)
+    assert case in TABLE
+    (x, w, gy), plain = _case_data(case)
+    g = torch.Generator().manual_seed(5)
+    bias = torch.randn(case[0] * case[2], generator=g)
+    sink = (torch.randn(w.shape, generator=g) * plain["dw"][0].abs().mean()).float()
+    got = run_case(case, x, w, gy, bias=bias, sink=sink)
+    held(case, got, B.refs(case, x, w, gy, bias=bias, sink=sink), "bias+accumulate " + B.case_id(case))
+    assert not torch.equal(got["dw"], sink)
+
+
+FUNCTION_LAYERS = [dict(in_channels=32, out_channels=64, kernel_size=5, padding=4, dilation=2, stride=2, groups=4, bias=True),
+                   dict(in_channels=80, out_channels=96, kernel_size=3, padding=1, groups=2, bias=True)]
+
+
+@pytest.mark.parametrize("kw", FUNCTION_LAYERS, ids=["5x5-s2-d2-8to16", "3x3-40to48"])
+def test_conv2d_function_gives_the_bits_of_the_raw_calls(kw):
+    from u2pl_amd import nn as K
+    conv = K.Conv2d(**kw)
+    groups, k = conv.groups, kw["kernel_size"]
+    case = (groups, conv.in_channels // groups, conv.out_channels // groups, k, k, 13, 11, conv.stride, conv.padding, conv.dilation, 2)
+    assert case[1] != case[2] and K.gconv_constraint(conv.in_channels, conv.out_channels, groups, conv.stride) is None
+    x, w, gy = B.operands(case, seed=4)
+    bias = torch.randn(conv.out_channels, generator=torch.Generator().manual_seed(6))
+    with torch.no_grad():
+        conv.weight.copy_(w)
+        conv.bias.copy_(bias)
+    conv = conv.to(DEV)                                       # plain parameters: no arena, the gradients come back through autograd
+    xd = x.to(DEV).contiguous(memory_format=CL).requires_grad_(True)
+    with recorded_calls(K) as seen:
+        y = conv(xd)
+        y.backward(gy.to(DEV).contiguous(memory_format=CL))
+        K.wgrad_stream_sync()
+    torch.cuda.synchronize()
+    assert [len(seen.get("u2pl_gconv2d" + s, [])) for s in ("_fwd_f32", "_dgrad_f32", "_wgrad_f32")] == [1, 1, 1]
+    assert not [n_ for n_ in seen if n_.startswith("u2pl_dwconv2d") or n_.startswith("u2pl_conv2d")]
+    raw = run_case(case, x, w, gy, bias=bias)
+    held(case, raw, B.refs(case, x, w, gy, bias=bias), "function " + B.case_id(case))
+    for got, name in ((y.detach(), "y"), (xd.grad, "dx"), (conv.weight.grad, "dw")):
+        assert torch.equal(got.cpu().view(torch.int32), raw[name].contiguous().view(torch.int32)), name
+    assert float((conv.bias.grad.cpu().double() - gy.double().sum((0, 2, 3))).abs().max()) <= \
+        (gy.shape[0] * gy.shape[2] * gy.shape[3] + 2) * EPS * float(gy.double().abs().sum((0, 2, 3)).max())
+
+
+def test_grad_join_of_a_grouped_and_a_dense_consumer():
+    """x feeds a grouped 3x3 (8 -> 16 channels per group) and a dense 1x1 that share a GradJoin: x.grad is the sum of the two data
+    gradients, each within its own bound (the grouped one's above, the dense one's of tests/split_bounds.py), plus the one fp32
+    rounding of the sum -- whichever backward runs first"""
+    from u2pl_amd import nn as K
+    case = (4, 8, 16, 3, 3, 13, 11, 1, 1, 1, 2)
+    x, w, gy = B.operands(case, seed=7)
+    torch.manual_seed(8)
+    gc = K.Conv2d(32, 64, 3, padding=1, groups=4, bias=False)
+    with torch.no_grad():
+        gc.weight.copy_(w)
+    gc = gc.to(DEV)
+    pw = K.Conv2d(32, 32, 1, bias=False).to(DEV)
+    ga = gy.to(DEV).contiguous(memory_format=CL)
+    gb_cpu = torch.randn(2, 32, 13, 11)
+    gb = gb_cpu.to(DEV).contiguous(memory_format=CL)
+    xs = [x.to(DEV).contiguous(memory_format=CL).requires_grad_(True) for _ in range(2)]
+    with recorded_calls(K) as seen:
+        for order in (0, 1):
+            xj = xs[order]
+            join = K.grad_join(xj, 2)
+            assert join is not None
+            if order == 0:                                    # (autograd runs the later consumer's backward first)
+                ya = gc(xj, grad_link=join)
+                yb = pw(xj, grad_link=join)
+            else:
+                yb = pw(xj, grad_link=join)
+                ya = gc(xj, grad_link=join)
+            ((ya * ga).sum() + (yb * gb).sum()).backward()
+        K.wgrad_stream_sync()
+    torch.cuda.synchronize()
+    assert len(seen.get("u2pl_gconv2d_dgrad_f32", [])) == 2
+    ref_a, bound_a = B.refs(case, x, w, gy)["dx"]
+    ref_b, bound_b = conv_dx_bound(gb_cpu, pw.weight.detach().cpu(), (13, 11))
+    ref, part = ref_a + ref_b, bound_a + bound_b
+    assert float(ref_a.abs().max()) > 0 and float(ref_b.abs().max()) > 0
+    for order in (0, 1):
+        e = excess(xs[order].grad, ref, part + EPS * (ref.abs() + part))
+        print("grad join order %d: excess %.4f" % (order, e))
+        assert e <= 1.0, (order, e)
+    # ... and the join has added something: the grouped gradient alone misses the sum
+    assert excess(xs[0].grad, ref_a, bound_a) > 1.0
