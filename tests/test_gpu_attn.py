@@ -11,28 +11,24 @@ those values).
 The decoder against its float64 twin (torch float64: F.conv2d, F.batch_norm, softmax(scale q k^T) v per head):
 dec_nonlocal(in_planes=128, inner_planes=64, key_planes=32, value_planes=48, rep_head=True), the zero-initialised norm weight
 moved away from 0, Dropout2d p = 0, 4 x 128 x 9 x 9, train mode, kv_stride 1 and 2, heads 1 and 2; figures and yardstick are those of
-test_gpu_psp.test_pspnet_decoder_is_no_worse_than_the_deeplabv3_decoder: max|got - ref| / max|ref| of every output, dx and every
+decoder_harness.assert_no_worse_than_deeplabv3: max|got - ref| / max|ref| of every output, dx and every
 parameter gradient <= 2x the largest figure of dec_deeplabv3(in_planes=128, dilations=(1, 2, 12)) against its own twin.
 
 The whole path: ResNet-50 + dec_nonlocal through ModelBuilder at 65 x 65 (a 9 x 9 decoder input)."""
-import copy
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import attn_bounds as B
-from model_utils import net_cfg
+from decoder_harness import (DEV, SENT, D, Rows, Ws, _merge, _ptr, _seq64, _show, _twice, assert_default_config_is_untouched,
+                             assert_eval_forward_ignores_the_graph, assert_no_worse_than_deeplabv3, assert_replay_equals_eager,
+                             build_net, call, decoder_cfg, net_input, query, step_calls, train_steps)
 from split_bounds import recorded_calls
-from test_gpu_ocr import D, Rows, Ws, _merge, _ptr, _show, _twice, call, query
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CL = torch.channels_last
 f32, f64 = np.float32, np.float64
 AF, AB = "u2pl_attn_fwd_f32", "u2pl_attn_bwd_f32"
-SENT = B.sentinel()
 ALL = ("dq", "dk", "dv")
 SUBSETS = [tuple(n for i, n in enumerate(ALL) if m >> i & 1) for m in range(1, 8)]
 
@@ -258,7 +254,6 @@ def test_shapes_are_checked_before_any_call():
 
 # ---- the decoder against its float64 twin -------------------------------------------------------------------------------------
 def _nl_twin(dec, p, x):
-    from test_gpu_psp import _seq64
     f = _seq64(dec.conva, p, "conva", x)
     b = dec.nl
     q = F.conv2d(f, p["nl.query.weight"], p["nl.query.bias"])
@@ -273,102 +268,30 @@ def _nl_twin(dec, p, x):
     return dict(pred=F.conv2d(out, p["classifier.weight"], p["classifier.bias"]), rep=_seq64(dec.representation, p, "representation", out))
 
 
-def _nl_figures(dec, keys=("pred", "rep"), seed=0):
-    """test_gpu_psp._figures on dec_nonlocal (same seeds, same input, same figure max|got - ref| / max|ref|) but for one scale: the
-    key's bias adds q[p] . b to EVERY score of the query p, which the softmax does not see, so its gradient is 0 in exact
-    arithmetic (the float64 twin gives roundings of 1e-17) and max|ref| is no scale for it.  The value's bias is the same case:
-    the weights of a query sum to 1, so it adds one constant per channel to the block's projection, which the train-mode
-    BatchNorm behind it subtracts with the mean.  Their figures are taken relative to the gradient of the same convolution's
-    weight summed over the input channels: what they would be made of if the shift did matter (test_gpu_cc._cc_figures does the
-    same for its key bias)"""
-    from u2pl_amd import nn as Kn
-    for m in dec.modules():
-        if isinstance(m, torch.nn.Dropout2d):
-            m.p = 0.0
-    with torch.no_grad():
-        for n_, q in dec.named_parameters():
-            if q.dim() == 1 and isinstance(dec.get_submodule(n_.rsplit(".", 1)[0]), Kn.BatchNorm2d):   # affine away from (1, 0); nl's from 0
-                q.copy_(torch.rand(q.shape) + 0.5 if n_.endswith("weight") else torch.randn(q.shape) * 0.1)
-    dec = dec.to(DEV).train()
-    sd = {n_: t.detach().clone() for n_, t in dec.state_dict().items()}
-    g = torch.Generator().manual_seed(seed + 1)
-    x = torch.relu(torch.randn(4, 128, 9, 9, generator=g)).contiguous(memory_format=CL)
-    xd = x.to(DEV).requires_grad_(True)
-    out = dec(xd)
-    G = {n_: torch.randn(out[n_].shape, generator=g) for n_ in keys}
-    sum((out[n_] * G[n_].to(DEV).contiguous(memory_format=CL)).sum() for n_ in keys).backward()
-    Kn.wgrad_stream_sync()
-    torch.cuda.synchronize()
-    p = {n_: t.detach().cpu().double().clone().requires_grad_(True) for n_, t in sd.items() if t.is_floating_point() and "running" not in n_}
-    x64 = x.double().clone().requires_grad_(True)
-    ref_out = _nl_twin(dec, p, x64)
-    sum((ref_out[n_] * G[n_].double()).sum() for n_ in keys).backward()
-    ref = dict(dx=x64.grad, **{n_: ref_out[n_].detach() for n_ in keys}, **{n_: t.grad for n_, t in p.items()})
-    got = dict(dx=xd.grad, **{n_: out[n_] for n_ in keys})
-    for n_, q in dec.named_parameters():
-        assert q.grad is not None, n_
-        got[n_] = q.grad
-    assert set(got) == set(ref)
-    scale = {n_: float(ref[n_].abs().max()) for n_ in got}
-    for n_ in [n_ for n_ in got if n_.endswith((".key.bias", ".value.bias"))]:
-        wsum = float(ref[n_[:-4] + "weight"].abs().sum(1).max())
-        assert scale[n_] <= 1e-10 * wsum                          # zero but for float64 roundings of sums of that size
-        scale[n_] = wsum
-    fig = {n_: float((got[n_].detach().cpu().double() - ref[n_]).abs().max()) / scale[n_] for n_ in got}
-    return fig, {n_: tuple(ref[n_].shape) for n_ in got}
+# the key's bias adds q[p] . b to EVERY score of the query p, which the softmax does not see: its exact gradient is zero.  The
+# value's bias is the same case: the weights of a query sum to 1, so it adds one constant per channel to the block's projection,
+# which the train-mode BatchNorm behind it subtracts with the mean.  (Zero but for float64 roundings of sums of the weight's size.)
+KEY_AND_VALUE_BIAS_ARE_ZERO = ((".key.bias", ".value.bias"), lambda scale, wsum: scale <= 1e-10 * wsum)
 
 
 @pytest.mark.parametrize("kv_stride,heads", [(1, 1), (2, 2), (2, 1), (1, 2)])
 def test_nonlocal_decoder_is_no_worse_than_the_deeplabv3_decoder(kv_stride, heads):
-    from test_gpu_psp import _figures, _v3_twin
-    from u2pl_amd.models.decoder import dec_deeplabv3, dec_nonlocal
-    torch.manual_seed(0)
-    v3, v3shape = _figures(dec_deeplabv3(in_planes=128, dilations=(1, 2, 12)), _v3_twin, ("pred",))
-    torch.manual_seed(0)
-    dec = dec_nonlocal(in_planes=128, inner_planes=64, key_planes=32, value_planes=48, heads=heads, kv_stride=kv_stride, rep_head=True)
-    nl, nshape = _nl_figures(dec)
-    top = max(v3.values())
-    print("\ndecoder figures (max|got - ref| / max|ref|); largest dec_deeplabv3 figure %.3e" % top)
-    for n in sorted(nl):
-        print("   %-36s %-18s dec_nonlocal  %.3e" % (n, nshape[n], nl[n]))
-    assert {"pred", "rep", "dx", "conva.0.weight", "nl.query.weight", "nl.key.bias", "nl.value.weight", "nl.project.0.weight", "nl.project.1.weight",
-            "convb.0.weight", "bottleneck.0.weight", "classifier.bias", "representation.4.weight"} <= set(nl)
-    assert all(np.isfinite(val) for val in nl.values()) and all(np.isfinite(val) for val in v3.values())
-    bad = {n: (val, top) for n, val in nl.items() if not val <= 2 * top}
-    assert not bad, bad
+    """(figures re-draws every norm's affine pair: the block's zero-initialised norm weight too, so the attention is live)"""
+    from u2pl_amd.models.decoder import dec_nonlocal
+    assert_no_worse_than_deeplabv3(
+        "dec_nonlocal", lambda: dec_nonlocal(in_planes=128, inner_planes=64, key_planes=32, value_planes=48, heads=heads,
+                                             kv_stride=kv_stride, rep_head=True), _nl_twin, ("pred", "rep"),
+        {"pred", "rep", "dx", "conva.0.weight", "nl.query.weight", "nl.key.bias", "nl.value.weight", "nl.project.0.weight", "nl.project.1.weight",
+         "convb.0.weight", "bottleneck.0.weight", "classifier.bias", "representation.4.weight"}, zero_grad=KEY_AND_VALUE_BIAS_ARE_ZERO)
 
 
 # ---- the whole path -----------------------------------------------------------------------------------------------------------
-S_NET = 65
 NL_DECODER = dict(type="u2pl.models.decoder.dec_nonlocal", kwargs=dict(rep_head=True))
-
-
-def _nl_cfg():
-    cfg = net_cfg("resnet50", 19, True)
-    cfg["encoder"]["kwargs"]["zero_init_residual"] = False   # (a zero bn3 weight would cut the gradient of each block's branch)
-    cfg["decoder"] = copy.deepcopy(NL_DECODER)
-    return cfg
 
 
 @pytest.fixture(scope="module")
 def nlnet():
-    from u2pl_amd.models.model_helper import ModelBuilder
-    torch.manual_seed(0)
-    model = ModelBuilder(_nl_cfg()).to(DEV)
-    x = torch.randn(4, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(1)).to(DEV)
-    return model, x
-
-
-def _step_calls(model, x, keys=("pred", "rep", "aux")):
-    from u2pl_amd import nn as Kn
-    with recorded_calls(Kn) as seen:
-        outs = model(x)
-        g = torch.Generator().manual_seed(2)
-        loss = sum((outs[n] * torch.randn(outs[n].shape, generator=g).to(DEV)).sum() for n in keys)
-        loss.backward()
-        Kn.wgrad_stream_sync()
-    torch.cuda.synchronize()
-    return seen, outs
+    return build_net(decoder_cfg(NL_DECODER)), net_input()
 
 
 QKV = ["decoder.nl.%s.weight" % n for n in ("query", "key", "value")]
@@ -383,7 +306,7 @@ def test_nonlocal_train_step_reaches_every_parameter_and_the_norm_weight_leaves_
     before = {n_: p.detach().clone() for n_, p in model.named_parameters() if n_ in QKV}
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     opt.zero_grad(set_to_none=True)
-    seen, outs = _step_calls(model, x)
+    seen, outs = step_calls(model, x)
     assert sorted(outs) == ["aux", "pred", "rep"] and outs["pred"].shape == (4, 19, 9, 9)
     assert [len(seen[n_]) for n_ in (AF, AB)] == [1, 1]
     assert seen[AF][0][7:13] == (4, 1, 81, 81, 64, 256) and seen[AF][0][6] == 0.125
@@ -398,9 +321,9 @@ def test_nonlocal_train_step_reaches_every_parameter_and_the_norm_weight_leaves_
     assert bool(w0.detach().ne(0).any())                                        # after the first SGD step it has left 0
     assert all(torch.equal(params[n_].detach(), before[n_]) for n_ in QKV)
     opt.zero_grad(set_to_none=True)
-    _step_calls(model, x)                                                       # the attention is live now: every parameter moves
+    step_calls(model, x)                                                        # the attention is live now: every parameter moves
     bad = [n_ for n_, p in model.named_parameters() if not bool(torch.isfinite(p.grad).all())]
-    # (the key's and the value's bias have a zero gradient in exact arithmetic: _nl_figures)
+    # (the key's and the value's bias have a zero gradient in exact arithmetic: KEY_AND_VALUE_BIAS_ARE_ZERO)
     zero = [n_ for n_, p in model.named_parameters() if not bool(p.grad.ne(0).any()) and not n_.endswith(("nl.key.bias", "nl.value.bias"))]
     assert not bad and not zero, (bad, zero)
     opt.step()
@@ -410,81 +333,22 @@ def test_nonlocal_train_step_reaches_every_parameter_and_the_norm_weight_leaves_
 
 
 def test_nonlocal_eval_forward_is_the_same_with_and_without_a_graph(nlnet):
-    model, x = nlnet
-    model.eval()
-    try:
-        with torch.no_grad():
-            a = model(x)
-        b = model(x)
-        assert b["pred"].requires_grad and a["pred"].shape == (4, 19, 9, 9) and a["rep"].shape == (4, 256, 9, 9)
-        for n in ("pred", "rep"):
-            assert bool(torch.isfinite(a[n]).all()) and torch.equal(a[n], b[n].detach()), n
-    finally:
-        model.train()
+    assert_eval_forward_ignores_the_graph(nlnet)
 
 
 def test_default_config_makes_no_attn_call_and_the_same_calls_after_a_nonlocal_step(nlnet):
-    from u2pl_amd.models.model_helper import ModelBuilder
-    counts = []
-    for nl_first in (False, True):
-        if nl_first:
-            nlnet[0].train()
-            assert AF in _step_calls(*nlnet)[0]
-            nlnet[0].zero_grad(set_to_none=True)
-        torch.manual_seed(0)
-        model = ModelBuilder(net_cfg("resnet50", 19, True)).to(DEV).train()
-        x = torch.randn(2, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(3)).to(DEV)
-        seen, _ = _step_calls(model, x)
-        assert len(seen) > 10
-        assert not [n_ for n_ in seen if n_.startswith("u2pl_attn_")]
-        counts.append({n: len(a) for n, a in seen.items()})
-    assert counts[0] == counts[1]
-
-
-def _train(monkeypatch, graphs_on, steps=4, S=S_NET):
-    """tests/test_gpu_psp.py::_train with the non-local decoder: the block's norm weight starts at 0 and SGD moves it between the steps"""
-    from u2pl_amd import configs, graphs as G
-    from u2pl_amd.models.model_helper import ModelBuilder
-    from u2pl_amd.trainer import SemiTrainer
-    from u2pl_amd.utils.loss_helper import get_criterion
-
-    monkeypatch.setenv("U2PL_GRAPHS", "1" if graphs_on else "0")
-    cfg = configs.cityscapes_semi(arch="resnet50", crop=S, batch_size=2, sync_bn=False, epochs=20)
-    cfg["net"]["decoder"] = dict(type=NL_DECODER["type"], kwargs=dict(rep_head=True, kv_stride=2, heads=2))
-    cfg["criterion"]["kwargs"]["min_kept"] = 1500
-    cfg["trainer"]["contrastive"]["current_class_threshold"] = 0.055
-    torch.manual_seed(0)
-    model, teacher = ModelBuilder(copy.deepcopy(cfg["net"])), ModelBuilder(copy.deepcopy(cfg["net"]))
-    teacher.load_state_dict(model.state_dict())
-    model, teacher = model.to(DEV), teacher.to(DEV)
-    tr = SemiTrainer(cfg, model, teacher, get_criterion(cfg), steps_per_epoch=4)
-    g = torch.Generator().manual_seed(5)
-    stats0 = dict(G.STATS)
-    meters, norms = [], []
-    for step in range(steps):
-        il, iu = torch.randn(2, 3, S, S, generator=g), torch.randn(2, 3, S, S, generator=g)
-        ll = torch.randint(0, 19, (2, S, S), generator=g)
-        ll[:, :6] = 255
-        np.random.seed(30 + step)
-        torch.manual_seed(40 + step)
-        torch.cuda.manual_seed(50 + step)
-        meters.append(tr.train_step(il.to(DEV), ll.to(DEV), iu.to(DEV), epoch=step // 4).cpu().numpy())
-        norms.append(float(model.decoder.nl.project[1].weight.detach().abs().sum()))
-    torch.cuda.synchronize()
-    return dict(meters=np.stack(meters), w=tr.arena.flat.clone(), t=tr.t_arena.flat.clone(), norms=norms,
-                stats={n: G.STATS[n] - stats0[n] for n in stats0})
+    assert_default_config_is_untouched(nlnet, AF, "u2pl_attn_")
 
 
 def test_nonlocal_graph_replay_is_bit_identical_to_eager(monkeypatch):
-    a = _train(monkeypatch, True)
-    b = _train(monkeypatch, False)
-    print("graph stats", a["stats"], "|norm weight| after each step", a["norms"])
-    assert a["stats"]["replays"] > 0 and a["stats"]["aborted"] == 0 and b["stats"]["replays"] == 0
-    assert np.isfinite(a["meters"]).all()
-    assert a["norms"][0] != 0.0 and len(set(a["norms"])) == len(a["norms"])         # the norm weight moves at every step
-    assert a["norms"] == b["norms"]
-    assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
-    assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+    """two heads over strided keys; the block's norm weight starts at 0 and SGD moves it between the steps"""
+    two_heads = dict(type=NL_DECODER["type"], kwargs=dict(rep_head=True, kv_stride=2, heads=2))
+    a, b = (train_steps(monkeypatch, on, lambda cfg: cfg["net"].update(decoder=two_heads),
+                        probe=lambda model: float(model.decoder.nl.project[1].weight.detach().abs().sum())) for on in (True, False))
+    print("graph stats", a["stats"], "|norm weight| after each step", a["probes"])
+    assert_replay_equals_eager(a, b)
+    assert a["probes"][0] != 0.0 and len(set(a["probes"])) == len(a["probes"])         # the norm weight moves at every step
+    assert a["probes"] == b["probes"]
 
 
 # ---- prediction ----------------------------------------------------------------------------------------------------------------

@@ -24,20 +24,17 @@ quotient means nothing; for those biases the denominator is max_c sum_pixels |dy
 produces them.
 
 The whole path: ResNet-50 + the separable DeepLabv3+ decoder through ModelBuilder at 65 x 65."""
-import copy
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import dw_bounds as B
+from decoder_harness import CL, DEV, assert_replay_equals_eager, build_net, decoder_cfg, net_input, step_calls, train_steps
 from model_utils import net_cfg
 from split_bounds import EPS, recorded_calls
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CL = torch.channels_last
 STEM = "u2pl_dwconv2d"
 
 
@@ -319,36 +316,15 @@ def test_separable_decoder_is_no_worse_than_the_dense_decoder():
 
 
 # ---- the whole path -----------------------------------------------------------------------------------------------------------
-S_NET = 65
-
-
 def _sep_cfg():
-    cfg = net_cfg("resnet50", 19, True)
-    cfg["encoder"]["kwargs"]["zero_init_residual"] = False   # (a zero bn3 weight would cut the gradient of each block's branch)
+    cfg = decoder_cfg()
     cfg["decoder"]["kwargs"]["separable"] = True
     return cfg
 
 
 @pytest.fixture(scope="module")
 def sepnet():
-    from u2pl_amd.models.model_helper import ModelBuilder
-    torch.manual_seed(0)
-    model = ModelBuilder(_sep_cfg()).to(DEV)
-    g = torch.Generator().manual_seed(1)
-    x = torch.randn(4, 3, S_NET, S_NET, generator=g).to(DEV)
-    return model, x
-
-
-def _step_calls(model, x):
-    from u2pl_amd import nn as K
-    with recorded_calls(K) as seen:
-        outs = model(x)
-        g = torch.Generator().manual_seed(2)
-        loss = sum((outs[k] * torch.randn(outs[k].shape, generator=g).to(DEV)).sum() for k in ("pred", "rep", "aux"))
-        loss.backward()
-        K.wgrad_stream_sync()
-    torch.cuda.synchronize()
-    return seen
+    return build_net(_sep_cfg()), net_input()
 
 
 def test_separable_train_step_reaches_every_parameter(sepnet):
@@ -357,7 +333,7 @@ def test_separable_train_step_reaches_every_parameter(sepnet):
     model.train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     opt.zero_grad(set_to_none=True)
-    seen = _step_calls(model, x)
+    seen, _ = step_calls(model, x)
     n_dw = sum(1 for m in model.modules() if isinstance(m, K.Conv2d) and m.groups != 1)
     assert n_dw == 8
     for name in (STEM + "_fwd_f32", STEM + "_dgrad_f32", STEM + "_wgrad_f32"):
@@ -391,8 +367,7 @@ def test_separable_eval_forward_is_the_same_with_and_without_a_graph(sepnet):
 def test_separable_state_dict_round_trip_and_a_dense_checkpoint_is_refused(sepnet):
     from u2pl_amd.models.model_helper import ModelBuilder
     model, x = sepnet
-    torch.manual_seed(99)
-    fresh = ModelBuilder(_sep_cfg()).to(DEV)
+    fresh = build_net(_sep_cfg(), seed=99)
     fresh.load_state_dict(model.state_dict())
     model.eval(), fresh.eval()
     try:
@@ -408,59 +383,18 @@ def test_separable_state_dict_round_trip_and_a_dense_checkpoint_is_refused(sepne
 
 
 def test_default_decoder_makes_no_depthwise_call_and_the_calls_of_a_model_built_without_the_keyword():
-    from u2pl_amd.models.model_helper import ModelBuilder
     counts = []
     for kw in ({}, dict(separable=False)):
         cfg = net_cfg("resnet50", 19, True)
         cfg["decoder"]["kwargs"].update(kw)
-        torch.manual_seed(0)
-        model = ModelBuilder(cfg).to(DEV).train()
-        x = torch.randn(2, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(3)).to(DEV)
-        seen = _step_calls(model, x)
+        seen, _ = step_calls(build_net(cfg).train(), net_input(2, 3))
         assert len(seen) > 10
         assert not [n_ for n_ in seen if n_.startswith(STEM) or n_.startswith("u2pl_gconv2d")]
         counts.append({k: len(v) for k, v in seen.items()})
     assert counts[0] == counts[1]
 
 
-def _train(monkeypatch, graphs_on, steps=4, S=S_NET):
-    """tests/test_gpu_gconv.py::_train with the separable decoder instead of the grouped encoder"""
-    from u2pl_amd import configs, graphs as G
-    from u2pl_amd.models.model_helper import ModelBuilder
-    from u2pl_amd.trainer import SemiTrainer
-    from u2pl_amd.utils.loss_helper import get_criterion
-
-    monkeypatch.setenv("U2PL_GRAPHS", "1" if graphs_on else "0")
-    cfg = configs.cityscapes_semi(arch="resnet50", crop=S, batch_size=2, sync_bn=False, epochs=20)
-    cfg["net"]["decoder"]["kwargs"]["separable"] = True
-    cfg["criterion"]["kwargs"]["min_kept"] = 1500
-    cfg["trainer"]["contrastive"]["current_class_threshold"] = 0.055
-    torch.manual_seed(0)
-    model, teacher = ModelBuilder(copy.deepcopy(cfg["net"])), ModelBuilder(copy.deepcopy(cfg["net"]))
-    teacher.load_state_dict(model.state_dict())
-    model, teacher = model.to(DEV), teacher.to(DEV)
-    tr = SemiTrainer(cfg, model, teacher, get_criterion(cfg), steps_per_epoch=4)
-    g = torch.Generator().manual_seed(5)
-    stats0 = dict(G.STATS)
-    meters = []
-    for step in range(steps):
-        il, iu = torch.randn(2, 3, S, S, generator=g), torch.randn(2, 3, S, S, generator=g)
-        ll = torch.randint(0, 19, (2, S, S), generator=g)
-        ll[:, :6] = 255
-        np.random.seed(30 + step)
-        torch.manual_seed(40 + step)
-        torch.cuda.manual_seed(50 + step)
-        meters.append(tr.train_step(il.to(DEV), ll.to(DEV), iu.to(DEV), epoch=step // 4).cpu().numpy())
-    torch.cuda.synchronize()
-    return dict(meters=np.stack(meters), w=tr.arena.flat.clone(), t=tr.t_arena.flat.clone(),
-                stats={k: G.STATS[k] - stats0[k] for k in stats0})
-
-
 def test_separable_graph_replay_is_bit_identical_to_eager(monkeypatch):
-    a = _train(monkeypatch, True)
-    b = _train(monkeypatch, False)
+    a, b = (train_steps(monkeypatch, on, lambda cfg: cfg["net"]["decoder"]["kwargs"].update(separable=True)) for on in (True, False))
     print("graph stats", a["stats"])
-    assert a["stats"]["replays"] > 0 and a["stats"]["aborted"] == 0 and b["stats"]["replays"] == 0
-    assert np.isfinite(a["meters"]).all()
-    assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
-    assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+    assert_replay_equals_eager(a, b)

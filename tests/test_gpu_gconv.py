@@ -24,24 +24,21 @@ past M, the tail of dw) and behind the workspace, which is allocated at exactly 
 tests/test_gconv_cpu.py shows on an emulation that this bound on this table rejects seven one-line addressing mistakes that the
 table above cannot see.  Each case prints its excess (pytest -s); U2PL_GCONV_RECORD=path writes the largest |got - f64| / bound per
 entry point and kernel family as JSON (profiles/gconv_bounds.json is one such run: a record, not a threshold)."""
-import copy
 import functools
 import json
 import math
 import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import gconv_bounds as B
+from decoder_harness import CL, DEV, S_NET, assert_replay_equals_eager, build_net, decoder_cfg, net_input, step_calls, train_steps
 from model_utils import net_cfg
 from split_bounds import EPS, conv_dx_bound, excess, recorded_calls
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CL = torch.channels_last
 
 WIDTHS = [(32, 4), (32, 8), (8, 16), (4, 32), (2, 64), (3, 12)]                  # (groups, channels per group); last: generic width
 GEOMS = [(13, 11, 1, 1), (9, 17, 2, 1), (13, 11, 1, 2), (9, 17, 1, 4), (12, 10, 2, 2)]      # (H, W, stride, dil)
@@ -250,23 +247,15 @@ def test_resnext_block_is_no_worse_than_the_dense_block(stride, dil):
 
 
 # ---- the whole path -----------------------------------------------------------------------------------------------------------
-S_NET = 65
-
-
-def _resnext_cfg(zero_init=False):
-    cfg = net_cfg("resnet50", 19, True)
-    cfg["encoder"]["kwargs"].update(groups=32, width_per_group=4, zero_init_residual=zero_init)
+def _resnext_cfg():
+    cfg = decoder_cfg()
+    cfg["encoder"]["kwargs"].update(groups=32, width_per_group=4)
     return cfg
 
 
 @pytest.fixture(scope="module")
 def resnext():
-    from u2pl_amd.models.model_helper import ModelBuilder
-    torch.manual_seed(0)
-    model = ModelBuilder(_resnext_cfg()).to(DEV)
-    g = torch.Generator().manual_seed(1)
-    x = torch.randn(4, 3, S_NET, S_NET, generator=g).to(DEV)
-    return model, x
+    return build_net(_resnext_cfg()), net_input()
 
 
 def test_resnext_train_step_reaches_every_parameter(resnext):
@@ -275,13 +264,7 @@ def test_resnext_train_step_reaches_every_parameter(resnext):
     model.train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     opt.zero_grad(set_to_none=True)
-    with recorded_calls(K) as seen:
-        outs = model(x)
-        g = torch.Generator().manual_seed(2)
-        loss = sum((outs[k] * torch.randn(outs[k].shape, generator=g).to(DEV)).sum() for k in ("pred", "rep", "aux"))
-        loss.backward()
-        K.wgrad_stream_sync()
-    torch.cuda.synchronize()
+    seen, _ = step_calls(model, x)
     n_g = sum(1 for m in model.modules() if isinstance(m, K.Conv2d) and m.groups != 1)
     assert n_g == 16
     for name in ("u2pl_gconv2d_fwd_f32", "u2pl_gconv2d_dgrad_f32", "u2pl_gconv2d_wgrad_f32"):
@@ -312,10 +295,8 @@ def test_resnext_eval_forward_is_the_same_with_and_without_a_graph(resnext):
 
 
 def test_resnext_state_dict_round_trip_gives_the_same_forward(resnext):
-    from u2pl_amd.models.model_helper import ModelBuilder
     model, x = resnext
-    torch.manual_seed(99)
-    fresh = ModelBuilder(_resnext_cfg()).to(DEV)
+    fresh = build_net(_resnext_cfg(), seed=99)
     fresh.load_state_dict(model.state_dict())
     model.eval(), fresh.eval()
     try:
@@ -342,47 +323,11 @@ def test_dense_resnet50_step_makes_no_grouped_call():
     assert not [n_ for n_ in seen if n_.startswith("u2pl_gconv2d")]
 
 
-def _train(monkeypatch, graphs_on, steps=4, S=S_NET):
-    """tests/test_gpu_graphs.py::_run with a ResNeXt-50 32x4d encoder"""
-    from u2pl_amd import configs, graphs as G
-    from u2pl_amd.models.model_helper import ModelBuilder
-    from u2pl_amd.trainer import SemiTrainer
-    from u2pl_amd.utils.loss_helper import get_criterion
-
-    monkeypatch.setenv("U2PL_GRAPHS", "1" if graphs_on else "0")
-    cfg = configs.cityscapes_semi(arch="resnet50", crop=S, batch_size=2, sync_bn=False, epochs=20)
-    cfg["net"]["encoder"]["kwargs"].update(groups=32, width_per_group=4)
-    cfg["criterion"]["kwargs"]["min_kept"] = 1500
-    cfg["trainer"]["contrastive"]["current_class_threshold"] = 0.055
-    torch.manual_seed(0)
-    model, teacher = ModelBuilder(copy.deepcopy(cfg["net"])), ModelBuilder(copy.deepcopy(cfg["net"]))
-    teacher.load_state_dict(model.state_dict())
-    model, teacher = model.to(DEV), teacher.to(DEV)
-    tr = SemiTrainer(cfg, model, teacher, get_criterion(cfg), steps_per_epoch=4)
-    g = torch.Generator().manual_seed(5)
-    stats0 = dict(G.STATS)
-    meters = []
-    for step in range(steps):
-        il, iu = torch.randn(2, 3, S, S, generator=g), torch.randn(2, 3, S, S, generator=g)
-        ll = torch.randint(0, 19, (2, S, S), generator=g)
-        ll[:, :6] = 255
-        np.random.seed(30 + step)
-        torch.manual_seed(40 + step)
-        torch.cuda.manual_seed(50 + step)
-        meters.append(tr.train_step(il.to(DEV), ll.to(DEV), iu.to(DEV), epoch=step // 4).cpu().numpy())
-    torch.cuda.synchronize()
-    return dict(meters=np.stack(meters), w=tr.arena.flat.clone(), t=tr.t_arena.flat.clone(),
-                stats={k: G.STATS[k] - stats0[k] for k in stats0})
-
-
 def test_resnext_graph_replay_is_bit_identical_to_eager(monkeypatch):
-    a = _train(monkeypatch, True)
-    b = _train(monkeypatch, False)
+    a, b = (train_steps(monkeypatch, on, lambda cfg: cfg["net"]["encoder"]["kwargs"].update(groups=32, width_per_group=4))
+            for on in (True, False))
     print("graph stats", a["stats"])
-    assert a["stats"]["replays"] > 0 and a["stats"]["aborted"] == 0 and b["stats"]["replays"] == 0
-    assert np.isfinite(a["meters"]).all()
-    assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
-    assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+    assert_replay_equals_eager(a, b)
 
 
 # ---- every width, tap and pixel edge: the table of tests/gconv_bounds.py in sentinel frames -------------------------------------

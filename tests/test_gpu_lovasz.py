@@ -11,9 +11,9 @@ import torch
 
 import loss_bounds as LB
 import lovasz_bounds as V
+from decoder_harness import DEV, S_NET, assert_replay_equals_eager, train_steps
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 TILE = V.TILE
 SENT = 0x5EA7BEEF                   # sentinel word framing the buffers
 GUARD = 64
@@ -277,61 +277,36 @@ def test_criterion_lovasz_against_float64(aux_weight, ce_w, lv_w, mode):
 
 
 # ---- trainers ------------------------------------------------------------------------------------------------------------------------
-S_NET = 65
-
-
-def _lovasz_cfg(S=S_NET):
-    from u2pl_amd import configs
-    cfg = configs.cityscapes_semi(arch="resnet50", crop=S, batch_size=2, sync_bn=False, epochs=20)
+def _use_lovasz(cfg):
     cfg["criterion"] = dict(type="lovasz", kwargs=dict(ce_weight=1.0, lovasz_weight=1.0, classes="present"))
+
+
+def _lovasz_cfg():
+    from u2pl_amd import configs
+    cfg = configs.cityscapes_semi(arch="resnet50", crop=S_NET, batch_size=2, sync_bn=False, epochs=20)
+    _use_lovasz(cfg)
     cfg["trainer"]["contrastive"]["current_class_threshold"] = 0.055
     return cfg
 
 
-def _train(monkeypatch, graphs_on, steps=4, S=S_NET, record=None):
-    from u2pl_amd import graphs as G
-    from u2pl_amd.models.model_helper import ModelBuilder
-    from u2pl_amd.trainer import SemiTrainer
-    from u2pl_amd.utils.loss_helper import get_criterion
-
-    monkeypatch.setenv("U2PL_GRAPHS", "1" if graphs_on else "0")
-    cfg = _lovasz_cfg(S)
-    torch.manual_seed(0)
-    model, teacher = ModelBuilder(copy.deepcopy(cfg["net"])), ModelBuilder(copy.deepcopy(cfg["net"]))
-    teacher.load_state_dict(model.state_dict())
-    model, teacher = model.to(DEV), teacher.to(DEV)
-    crit = get_criterion(cfg)
-    fn = crit
-    if record is not None:
-        def fn(preds, target):
-            record.append(([p.detach().cpu().numpy().copy() for p in preds], target.cpu().numpy().copy()))
-            return crit(preds, target)
-    tr = SemiTrainer(cfg, model, teacher, fn, steps_per_epoch=4)
-    g = torch.Generator().manual_seed(5)
-    stats0 = dict(G.STATS)
-    meters = []
-    for step in range(steps):
-        il, iu = torch.randn(2, 3, S, S, generator=g), torch.randn(2, 3, S, S, generator=g)
-        ll = torch.randint(0, 19, (2, S, S), generator=g)
-        ll[:, :6] = 255
-        np.random.seed(30 + step)
-        torch.manual_seed(40 + step)
-        torch.cuda.manual_seed(50 + step)
-        meters.append(tr.train_step(il.to(DEV), ll.to(DEV), iu.to(DEV), epoch=step // 4).cpu().numpy())
-    torch.cuda.synchronize()
-    return dict(meters=np.stack(meters), w=tr.arena.flat.clone(), t=tr.t_arena.flat.clone(),
-                stats={k: G.STATS[k] - stats0[k] for k in stats0})
-
-
 def test_semi_step_with_lovasz_eager_and_replayed(monkeypatch):
+    """the eager run's criterion is wrapped: what it was handed at each step is recomputed in float64 below"""
+    from u2pl_amd.utils import loss_helper
     rec = []
-    b = _train(monkeypatch, False, record=rec)
-    a = _train(monkeypatch, True)
+
+    def recording(cfg, real=loss_helper.get_criterion):
+        crit = real(cfg)
+
+        def fn(preds, target):
+            rec.append(([p.detach().cpu().numpy().copy() for p in preds], target.cpu().numpy().copy()))
+            return crit(preds, target)
+        return fn
+    with monkeypatch.context() as m:
+        m.setattr(loss_helper, "get_criterion", recording)
+        b = train_steps(m, False, _use_lovasz)
+    a = train_steps(monkeypatch, True, _use_lovasz)
     print("graph stats", a["stats"], "meters", a["meters"])
-    assert a["stats"]["replays"] > 0 and a["stats"]["aborted"] == 0 and b["stats"]["replays"] == 0
-    assert np.isfinite(a["meters"]).all()
-    assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
-    assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+    assert_replay_equals_eager(a, b)
     assert len(rec) == len(b["meters"])
     for (preds, target), m in zip(rec, b["meters"]):
         ref, _ = _criterion_ref(preds[0], preds[1], target, 0.4, 1.0, 1.0, "present")

@@ -10,101 +10,25 @@ forward's m, f and w rounded to fp32 (ocr_bounds: the references are evaluated o
 
 The decoder against its float64 twin (torch softmax / einsum, F.conv2d, F.batch_norm): dec_ocrnet(in_planes=128, inner_planes=64,
 key_planes=32, rep_head=True), Dropout2d p = 0, 4 x 128 x 9 x 9, train mode; figures and yardstick are those of
-test_gpu_psp.test_pspnet_decoder_is_no_worse_than_the_deeplabv3_decoder: max|got - ref| / max|ref| of every output, dx and every
+decoder_harness.assert_no_worse_than_deeplabv3: max|got - ref| / max|ref| of every output, dx and every
 parameter gradient <= 2x the largest figure of dec_deeplabv3(in_planes=128, dilations=(1, 2, 12)) against its own twin.
 
 The whole path: ResNet-50 + dec_ocrnet through ModelBuilder at 65 x 65 (a 9 x 9 decoder input)."""
-import copy
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import ocr_bounds as B
-from model_utils import net_cfg
+from decoder_harness import (CL, DEV, S_NET, SENT, D, Rows, Ws, _merge, _ptr, _seq64, _show, _twice,
+                             assert_default_config_is_untouched, assert_eval_forward_ignores_the_graph,
+                             assert_no_worse_than_deeplabv3, assert_replay_equals_eager, build_net, call, decoder_cfg, net_input,
+                             query, step_calls, train_steps)
 from split_bounds import recorded_calls
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CL = torch.channels_last
 f32, f64 = np.float32, np.float64
 PF, PB, AF, AB = "u2pl_region_pool_fwd_f32", "u2pl_region_pool_bwd_f32", "u2pl_region_attn_fwd_f32", "u2pl_region_attn_bwd_f32"
-SENT = B.sentinel()
-
-
-def call(*a):
-    from u2pl_amd._lib import call as c
-    return c(*a)
-
-
-def query(*a):
-    from u2pl_amd._lib import lib, query as q
-    lib()
-    return q(*a)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-class Rows:
-    """rows [M, C] of a [N, M / N, C] array inside a buffer of M + 2 rows of ld floats filled with `fill`, starting at row 1 and
-    column `off`: NaN for an input (no kernel may read the gaps), the sentinel for an output (no kernel may write the frame).
-    wide: a channel-wide tensor (pitch a multiple of 4, 16-byte aligned base); else a K-wide one (any pitch >= K)"""
-
-    def __init__(self, shape, pitched, fill, data=None, wide=True):
-        self.shape = shape
-        M, C = shape[0] * shape[1], shape[2]
-        self.M, self.C = M, C
-        self.ld, self.off = ((C + 12, 8) if wide else (C + 5, 3)) if pitched else (C, 0)
-        host = np.full((M + 2, self.ld), fill, dtype=f32)
-        if data is not None:
-            host[1:M + 1, self.off:self.off + C] = np.asarray(data, dtype=f32).reshape(M, C)
-        self.buf = D(host)
-        self.ptr = self.buf[1:, self.off:]
-
-    def get(self):
-        return self.buf.cpu().numpy()[1:self.M + 1, self.off:self.off + self.C].copy().reshape(self.shape)
-
-    def assert_frame_intact(self, what):
-        bits = self.buf.cpu().numpy().view(np.uint32).copy()
-        bits[1:self.M + 1, self.off:self.off + self.C] = B.SENTINEL_BITS
-        assert (bits == B.SENTINEL_BITS).all(), f"{what}: wrote outside its {self.M} x {self.C} rows (ld {self.ld})"
-
-
-class Ws:
-    """a NaN-filled workspace of n floats followed by eight sentinels"""
-
-    def __init__(self, n):
-        self.n = n
-        host = np.full(n + 8, np.nan, dtype=f32)
-        host[n:] = SENT
-        self.buf = D(host)
-
-    def assert_tail_intact(self, what):
-        assert bool((self.buf[self.n:].view(torch.int32) == B.SENTINEL_BITS).all()), f"{what}: wrote past its {self.n} workspace floats"
-
-
-def _ptr(r):
-    return (None, 0) if r is None else (r.ptr, r.ld)
-
-
-def _twice(what, run, outs):
-    """run() twice into fresh sentinel-framed outputs made by outs() -> the first run's arrays; both runs must agree bit for bit"""
-    res = []
-    for _ in range(2):
-        o = outs()
-        ws = run(o)
-        torch.cuda.synchronize()
-        for k, r in o.items():
-            if r is not None:
-                r.assert_frame_intact("%s %s" % (what, k))
-        if ws is not None:
-            ws.assert_tail_intact(what)
-        res.append({k: r.get() for k, r in o.items() if r is not None})
-    assert all(B.bits_equal(res[0][k], res[1][k]) for k in res[0]), "two runs of %s differ" % what
-    return res[0]
 
 
 def raw_pool_fwd(s, x, scale, pitched):
@@ -196,14 +120,6 @@ def check_case(N, HW, K, C, family, pitched, variants):
         assert sorted(got) == sorted(want)
         up(**B.attn_bwd_excess(got, gy, w32, q, kk, v, sc))
     return worst
-
-
-def _merge(a, b):
-    return {k: max(a.get(k, 0.0), b.get(k, 0.0)) for k in set(a) | set(b)}
-
-
-def _show(what, worst):
-    print("\n  %s: largest error / bound  %s" % (what, "  ".join("%s %.3f" % (k, worst[k]) for k in sorted(worst))), end="")
 
 
 @pytest.mark.parametrize("K", B.OCR_K)
@@ -402,7 +318,6 @@ def test_concat_consumer_gradient_goes_in_as_the_add_operand():
 
 # ---- the decoder against its float64 twin -------------------------------------------------------------------------------------
 def _ocr_twin(dec, p, x):
-    from test_gpu_psp import _seq64
     feat = _seq64(dec.conv3x3, p, "conv3x3", x)
     r = _seq64(dec.region, p, "region", x)
     N, C, H, W = feat.shape
@@ -420,56 +335,21 @@ def _ocr_twin(dec, p, x):
 
 
 def test_ocrnet_decoder_is_no_worse_than_the_deeplabv3_decoder():
-    from test_gpu_psp import _figures, _v3_twin
-    from u2pl_amd.models.decoder import dec_deeplabv3, dec_ocrnet
-    torch.manual_seed(0)
-    v3, v3shape = _figures(dec_deeplabv3(in_planes=128, dilations=(1, 2, 12)), _v3_twin, ("pred",))
-    torch.manual_seed(0)
-    ocr, oshape = _figures(dec_ocrnet(in_planes=128, inner_planes=64, key_planes=32, rep_head=True), _ocr_twin, ("pred", "region", "rep"))
-    top = max(v3.values())
-    print("\ndecoder figures (max|got - ref| / max|ref|); largest dec_deeplabv3 figure %.3e" % top)
-    for k in sorted(v3):
-        print("   %-36s %-18s dec_deeplabv3 %.3e" % (k, v3shape[k], v3[k]))
-    for k in sorted(ocr):
-        print("   %-36s %-18s dec_ocrnet    %.3e" % (k, oshape[k], ocr[k]))
-    assert {"pred", "region", "rep", "dx", "conv3x3.0.weight", "region.3.bias", "f_pixel.4.weight", "f_object.3.weight", "f_down.1.bias",
-            "f_up.0.weight", "fuse.0.weight", "classifier.bias", "representation.4.weight"} <= set(ocr)
-    assert all(np.isfinite(v) for v in ocr.values()) and all(np.isfinite(v) for v in v3.values())
-    bad = {k: (v, top) for k, v in ocr.items() if not v <= 2 * top}
-    assert not bad, bad
+    from u2pl_amd.models.decoder import dec_ocrnet
+    assert_no_worse_than_deeplabv3(
+        "dec_ocrnet", lambda: dec_ocrnet(in_planes=128, inner_planes=64, key_planes=32, rep_head=True), _ocr_twin,
+        ("pred", "region", "rep"),
+        {"pred", "region", "rep", "dx", "conv3x3.0.weight", "region.3.bias", "f_pixel.4.weight", "f_object.3.weight", "f_down.1.bias",
+         "f_up.0.weight", "fuse.0.weight", "classifier.bias", "representation.4.weight"}, show_v3=True)
 
 
 # ---- the whole path -----------------------------------------------------------------------------------------------------------
-S_NET = 65
 OCR_DECODER = dict(type="u2pl.models.decoder.dec_ocrnet", kwargs=dict(rep_head=True))
-
-
-def _ocr_cfg():
-    cfg = net_cfg("resnet50", 19, True)
-    cfg["encoder"]["kwargs"]["zero_init_residual"] = False   # (a zero bn3 weight would cut the gradient of each block's branch)
-    cfg["decoder"] = copy.deepcopy(OCR_DECODER)
-    return cfg
 
 
 @pytest.fixture(scope="module")
 def ocrnet():
-    from u2pl_amd.models.model_helper import ModelBuilder
-    torch.manual_seed(0)
-    model = ModelBuilder(_ocr_cfg()).to(DEV)
-    x = torch.randn(4, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(1)).to(DEV)
-    return model, x
-
-
-def _step_calls(model, x, keys=("pred", "rep", "aux")):
-    from u2pl_amd import nn as Kn
-    with recorded_calls(Kn) as seen:
-        outs = model(x)
-        g = torch.Generator().manual_seed(2)
-        loss = sum((outs[k] * torch.randn(outs[k].shape, generator=g).to(DEV)).sum() for k in keys)
-        loss.backward()
-        Kn.wgrad_stream_sync()
-    torch.cuda.synchronize()
-    return seen, outs
+    return build_net(decoder_cfg(OCR_DECODER)), net_input()
 
 
 def test_ocrnet_train_step_reaches_every_parameter(ocrnet):
@@ -478,7 +358,7 @@ def test_ocrnet_train_step_reaches_every_parameter(ocrnet):
     model.train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     opt.zero_grad(set_to_none=True)
-    seen, outs = _step_calls(model, x, ("pred", "rep", "aux", "region"))
+    seen, outs = step_calls(model, x, ("pred", "rep", "aux", "region"))
     assert sorted(outs) == ["aux", "pred", "region", "rep"] and outs["region"].shape == (4, 19, 9, 9)
     assert [len(seen[n_]) for n_ in (PF, PB, AF, AB)] == [1, 1, 1, 1]
     assert seen[PF][0][5:9] == (4, 81, 19, 512) and seen[AF][0][7:11] == (4, 81, 19, 256)
@@ -496,78 +376,18 @@ def test_ocrnet_train_step_reaches_every_parameter(ocrnet):
 
 
 def test_ocrnet_eval_forward_is_the_same_with_and_without_a_graph(ocrnet):
-    model, x = ocrnet
-    model.eval()
-    try:
-        with torch.no_grad():
-            a = model(x)
-        b = model(x)
-        assert b["pred"].requires_grad and a["pred"].shape == (4, 19, 9, 9) and a["rep"].shape == (4, 256, 9, 9)
-        for k in ("pred", "rep", "region"):
-            assert bool(torch.isfinite(a[k]).all()) and torch.equal(a[k], b[k].detach()), k
-    finally:
-        model.train()
+    assert_eval_forward_ignores_the_graph(ocrnet, ("pred", "rep", "region"))
 
 
 def test_default_config_makes_no_region_call_and_the_same_calls_after_an_ocrnet_step(ocrnet):
-    from u2pl_amd.models.model_helper import ModelBuilder
-    counts = []
-    for ocr_first in (False, True):
-        if ocr_first:
-            ocrnet[0].train()
-            assert PF in _step_calls(*ocrnet)[0]
-            ocrnet[0].zero_grad(set_to_none=True)
-        torch.manual_seed(0)
-        model = ModelBuilder(net_cfg("resnet50", 19, True)).to(DEV).train()
-        x = torch.randn(2, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(3)).to(DEV)
-        seen, _ = _step_calls(model, x)
-        assert len(seen) > 10
-        assert not [n_ for n_ in seen if n_.startswith("u2pl_region")]
-        counts.append({k: len(v) for k, v in seen.items()})
-    assert counts[0] == counts[1]
-
-
-def _train(monkeypatch, graphs_on, steps=4, S=S_NET):
-    """tests/test_gpu_psp.py::_train with the OCR decoder; the meters' supervised loss holds the region term"""
-    from u2pl_amd import configs, graphs as G
-    from u2pl_amd.models.model_helper import ModelBuilder
-    from u2pl_amd.trainer import SemiTrainer
-    from u2pl_amd.utils.loss_helper import get_criterion
-
-    monkeypatch.setenv("U2PL_GRAPHS", "1" if graphs_on else "0")
-    cfg = configs.cityscapes_semi(arch="resnet50", crop=S, batch_size=2, sync_bn=False, epochs=20)
-    cfg["net"]["decoder"] = copy.deepcopy(OCR_DECODER)
-    cfg["criterion"]["kwargs"]["min_kept"] = 1500
-    cfg["trainer"]["contrastive"]["current_class_threshold"] = 0.055
-    torch.manual_seed(0)
-    model, teacher = ModelBuilder(copy.deepcopy(cfg["net"])), ModelBuilder(copy.deepcopy(cfg["net"]))
-    teacher.load_state_dict(model.state_dict())
-    model, teacher = model.to(DEV), teacher.to(DEV)
-    tr = SemiTrainer(cfg, model, teacher, get_criterion(cfg), steps_per_epoch=4)
-    g = torch.Generator().manual_seed(5)
-    stats0 = dict(G.STATS)
-    meters = []
-    for step in range(steps):
-        il, iu = torch.randn(2, 3, S, S, generator=g), torch.randn(2, 3, S, S, generator=g)
-        ll = torch.randint(0, 19, (2, S, S), generator=g)
-        ll[:, :6] = 255
-        np.random.seed(30 + step)
-        torch.manual_seed(40 + step)
-        torch.cuda.manual_seed(50 + step)
-        meters.append(tr.train_step(il.to(DEV), ll.to(DEV), iu.to(DEV), epoch=step // 4).cpu().numpy())
-    torch.cuda.synchronize()
-    return dict(meters=np.stack(meters), w=tr.arena.flat.clone(), t=tr.t_arena.flat.clone(),
-                stats={k: G.STATS[k] - stats0[k] for k in stats0})
+    assert_default_config_is_untouched(ocrnet, PF, "u2pl_region")
 
 
 def test_ocrnet_graph_replay_is_bit_identical_to_eager(monkeypatch):
-    a = _train(monkeypatch, True)
-    b = _train(monkeypatch, False)
+    """the meters' supervised loss holds the region term"""
+    a, b = (train_steps(monkeypatch, on, lambda cfg: cfg["net"].update(decoder=OCR_DECODER)) for on in (True, False))
     print("graph stats", a["stats"])
-    assert a["stats"]["replays"] > 0 and a["stats"]["aborted"] == 0 and b["stats"]["replays"] == 0
-    assert np.isfinite(a["meters"]).all()
-    assert np.array_equal(a["meters"], b["meters"]), (a["meters"], b["meters"])
-    assert torch.equal(a["w"], b["w"]) and torch.equal(a["t"], b["t"])
+    assert_replay_equals_eager(a, b)
 
 
 def test_ocrnet_region_loss_is_finite_and_reaches_only_the_region_head():
@@ -576,10 +396,7 @@ def test_ocrnet_region_loss_is_finite_and_reaches_only_the_region_head():
     with region_loss_weight = 0 gets the supervised loss back as it is"""
     from u2pl_amd import nn as Kn
     from u2pl_amd.trainer import add_region_loss
-    from u2pl_amd.models.model_helper import ModelBuilder
-    torch.manual_seed(0)
-    model = ModelBuilder(_ocr_cfg()).to(DEV).train()
-    x = torch.randn(4, 3, S_NET, S_NET, generator=torch.Generator().manual_seed(1)).to(DEV)
+    model, x = build_net(decoder_cfg(OCR_DECODER)).train(), net_input()
     label = torch.randint(0, 19, (2, S_NET, S_NET), generator=torch.Generator().manual_seed(2)).to(DEV)
     label[:, :6] = 255
     outs = model(x)

@@ -19,6 +19,46 @@ def _conv3x3_unit(in_planes, out_planes, norm_layer, separable, bias):
             norm_layer(out_planes), nn.ReLU(inplace=True), *tail]
 
 
+# ---- what the heads below share.  A head registers its submodules in one fixed order: every layer draws its initial values from
+# the generator as it is constructed, ParamArena lays parameters out in registration order and checkpoints are keyed by the names,
+# so a moved line is another model (tests/test_decoder_layout_cpu.py holds the order and the seeded values) -------------------------
+def _unit3x3(cin, cout, norm_layer, *tail):
+    """dense 3x3 (stride 1, padding 1, no bias) -> norm -> ReLU [-> tail]"""
+    return nn.Sequential(K.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, dilation=1, bias=False), norm_layer(cout),
+                         nn.ReLU(inplace=True), *tail)
+
+
+def _rep_tower(inner_planes, norm_layer):
+    """the `representation` tower beside a classifier, for the contrastive loss: 3x3 to 256 -> norm -> ReLU -> Dropout2d(0.1) ->
+    1x1 to 256 with bias"""
+    return nn.Sequential(*_unit3x3(inner_planes, 256, norm_layer, nn.Dropout2d(0.1)),
+                         K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+
+
+def _last_map(x):
+    """the encoder's four maps (fpn: true): the head reads the last"""
+    return x[-1] if isinstance(x, (list, tuple)) else x
+
+
+def _outputs(dec, feat, need_rep, **extra):
+    """{"pred": classifier(feat), **extra[, "rep": representation(feat)]} of a head whose classifier is one convolution"""
+    res = {"pred": dec.classifier(feat), **extra}
+    if dec.rep_head and need_rep:
+        res["rep"] = K.run_seq(dec.representation, feat)
+    return res
+
+
+def _check_planes(who, **planes):
+    for name, val in planes.items():
+        if int(val) < 4 or int(val) % 4:
+            raise ValueError("%s: %s (%r) must be a positive multiple of 4 (float4 rows)" % (who, name, val))
+
+
+def _check_num_classes(who, num_classes):
+    if not 2 <= int(num_classes) <= K.REGION_MAX_K:
+        raise ValueError("%s: 2 <= num_classes <= %d (what the loss path takes), got %r" % (who, K.REGION_MAX_K, num_classes))
+
+
 class dec_deeplabv3(nn.Module):
     def __init__(self, in_planes, num_classes=19, inner_planes=256, sync_bn=False, dilations=(12, 24, 36), separable=False):
         super().__init__()
@@ -75,8 +115,8 @@ class dec_pspnet(nn.Module):
     """Pyramid-pooling head (PSPNet, Zhao et al. 2017, section 3.2; no reference line: the reference has the two ASPP heads only).
     ppm.{i}: AdaptiveAvgPool2d(bins[i]) -> 1x1 (in_planes / len(bins), no bias) -> norm -> ReLU, up-sampled to the input's size
     (bilinear, align_corners=True) and concatenated behind the input; head: dense 3x3 from 2 in_planes to inner_planes -> norm
-    -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: a `representation` tower (3x3 to 256 -> norm -> ReLU ->
-    Dropout2d(0.1) -> 1x1 to 256) beside the classifier, on the head's output, for the contrastive loss.
+    -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: a `representation` tower (_rep_tower) beside the classifier,
+    on the head's output.
     All levels are pooled by one launch and the input's gradient is written by one gather (K.pyramid_pool)."""
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, sync_bn=False, bins=(1, 2, 3, 6), rep_head=False):
@@ -96,29 +136,19 @@ class dec_pspnet(nn.Module):
                 norm_layer(red),
                 nn.ReLU(inplace=True),
             ) for b in bins)
-        self.head = nn.Sequential(
-            K.Conv2d(2 * in_planes, inner_planes, kernel_size=3, stride=1, padding=1, dilation=1, bias=False),
-            norm_layer(inner_planes), nn.ReLU(inplace=True), nn.Dropout2d(0.1))
+        self.head = _unit3x3(2 * in_planes, inner_planes, norm_layer, nn.Dropout2d(0.1))
         self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
         if rep_head:
-            self.representation = nn.Sequential(
-                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
-                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
-                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+            self.representation = _rep_tower(inner_planes, norm_layer)
 
     def forward(self, x, need_rep=True):
-        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
-            x = x[-1]
+        x = _last_map(x)
         h, w = x.size()[-2:]
         x_pass, *pooled = K.pyramid_pool(x, self.bins)
         # independent conv -> BN -> ReLU units: under a process group their statistics share one packed exchange
         f = K.conv_bn_group([(m[1], m[2], p, True, None) for m, p in zip(self.ppm, pooled)])
         feat = K.cat_channels((x_pass, *(K.upsample_bilinear(t, (h, w)) for t in f)))
-        feat = K.run_seq(self.head, feat)
-        res = {"pred": self.classifier(feat)}
-        if self.rep_head and need_rep:
-            res["rep"] = K.run_seq(self.representation, feat)
-        return res
+        return _outputs(self, K.run_seq(self.head, feat), need_rep)
 
 
 def _unit1x1(in_planes, out_planes, norm_layer):
@@ -133,8 +163,8 @@ class dec_ocrnet(nn.Module):
     on the labelled images (region_loss_weight; output key "region").  The region features f = sum over an image's pixels of
     softmax_pixels(region) * pixel features (K.region_pool) are a [N, inner, K, 1] map; queries f_pixel(pixel features), keys
     f_object(f), values f_down(f), one head: y = softmax_k(q . k / sqrt(key_planes)) v (K.region_attention); fuse: 1x1 over
-    cat(f_up(y), pixel features) -> norm -> ReLU -> Dropout2d(0.05); classifier: 1x1 with bias.  rep_head: dec_pspnet's
-    `representation` tower on the fused features.  Out of scope, refused or absent: more than 255 classes (regions), several
+    cat(f_up(y), pixel features) -> norm -> ReLU -> Dropout2d(0.05); classifier: 1x1 with bias.  rep_head: the
+    `representation` tower (_rep_tower) on the fused features.  Out of scope, refused or absent: more than 255 classes (regions), several
     heads, a separable form, regions taken from the auxiliary head, OHEM on the region loss.  (Pixel-to-pixel attention is dec_ccnet's.)"""
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=256, sync_bn=False, rep_head=False,
@@ -150,9 +180,7 @@ class dec_ocrnet(nn.Module):
         self.rep_head = rep_head
         self.key_planes = key_planes
         self.region_loss_weight = float(region_loss_weight)
-        self.conv3x3 = nn.Sequential(
-            K.Conv2d(in_planes, inner_planes, kernel_size=3, stride=1, padding=1, dilation=1, bias=False),
-            norm_layer(inner_planes), nn.ReLU(inplace=True))
+        self.conv3x3 = _unit3x3(in_planes, inner_planes, norm_layer)
         self.region = nn.Sequential(
             *_unit1x1(in_planes, 256, norm_layer),
             K.Conv2d(256, num_classes, kernel_size=1, stride=1, padding=0, bias=True))
@@ -163,14 +191,10 @@ class dec_ocrnet(nn.Module):
         self.fuse = nn.Sequential(*_unit1x1(2 * inner_planes, inner_planes, norm_layer), nn.Dropout2d(0.05))
         self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
         if rep_head:
-            self.representation = nn.Sequential(
-                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
-                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
-                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+            self.representation = _rep_tower(inner_planes, norm_layer)
 
     def forward(self, x, need_rep=True):
-        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
-            x = x[-1]
+        x = _last_map(x)
         feat = K.run_seq(self.conv3x3, x)
         r = K.run_seq(self.region, x)
         feat_p, f = K.region_pool(feat, r)
@@ -180,10 +204,7 @@ class dec_ocrnet(nn.Module):
         kk = K.conv_bn(self.f_object[3], self.f_object[4], k1, relu=True)
         y = K.run_seq(self.f_up, K.region_attention(q, kk, v, self.key_planes ** -0.5))
         out = K.run_seq(self.fuse, K.cat_channels((y, feat_p)))
-        res = {"pred": self.classifier(out), "region": r}
-        if self.rep_head and need_rep:
-            res["rep"] = K.run_seq(self.representation, out)
-        return res
+        return _outputs(self, out, need_rep, region=r)
 
 
 class CrissCrossBlock(nn.Module):
@@ -201,12 +222,36 @@ class CrissCrossBlock(nn.Module):
         return K.criss_cross_attention(self.query(x), self.key(x), self.value(x), self.gamma, res=x, scale=1.0)
 
 
-class dec_ccnet(nn.Module):
+class _ContextHead(nn.Module):
+    """what dec_ccnet and dec_nonlocal share: conva: 3x3 to inner_planes -> norm -> ReLU; the subclass's context block(s); convb:
+    3x3 -> norm -> ReLU; bottleneck: 3x3 over cat(input, convb) -> norm -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias;
+    rep_head: the `representation` tower (_rep_tower) on the bottleneck.  A subclass checks its arguments, hands the block's own
+    to __init__ and supplies make_context(inner_planes, norm_layer, **those), which registers the block(s), and context(f), which
+    runs a feature map through them.  make_context is called between conva and convb: the registration order of the two heads."""
+
+    def __init__(self, in_planes, num_classes, inner_planes, sync_bn, rep_head, **context_args):
+        super().__init__()
+        norm_layer = norm_layer_for(sync_bn)
+        self.rep_head = rep_head
+        self.conva = _unit3x3(in_planes, inner_planes, norm_layer)
+        self.make_context(inner_planes, norm_layer, **context_args)
+        self.convb = _unit3x3(inner_planes, inner_planes, norm_layer)
+        self.bottleneck = _unit3x3(in_planes + inner_planes, inner_planes, norm_layer, nn.Dropout2d(0.1))
+        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        if rep_head:
+            self.representation = _rep_tower(inner_planes, norm_layer)
+
+    def forward(self, x, need_rep=True):
+        x = _last_map(x)
+        f = K.run_seq(self.convb, self.context(K.run_seq(self.conva, x)))
+        return _outputs(self, K.run_seq(self.bottleneck, K.cat_channels((x, f))), need_rep)
+
+
+class dec_ccnet(_ContextHead):
     """Criss-cross attention head (CCNet, Huang et al., ICCV 2019, section 3; no reference line: the reference has the two ASPP
-    heads only).  conva: 3x3 to inner_planes -> norm -> ReLU; cca: a CrissCrossBlock applied `recurrence` times (every pixel
-    attends to its own row and column, K.criss_cross_attention; two rounds give every pixel a path to every other); with
-    shared=False a ModuleList of `recurrence` blocks; convb: 3x3 -> norm -> ReLU; bottleneck: 3x3 over cat(input, convb) -> norm
-    -> ReLU -> Dropout2d(0.1); classifier: 1x1 with bias.  rep_head: dec_pspnet's `representation` tower on the bottleneck.
+    heads only): a _ContextHead whose block is cca: a CrissCrossBlock applied `recurrence` times (every pixel attends to its own
+    row and column, K.criss_cross_attention; two rounds give every pixel a path to every other); with shared=False a ModuleList
+    of `recurrence` blocks.
     A map with H + W - 1 > K.CC_MAX_L is refused (predict large images in sliding windows).  With shared=True and
     recurrence > 1 the block's gradient sinks are written once per round, which the bucketed all-reduce does not count: that
     combination is refused under a process group.  Out of scope, refused or absent: a fused q/k/v projection, a tiled cross,
@@ -214,34 +259,24 @@ class dec_ccnet(nn.Module):
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=64, recurrence=2, shared=True, sync_bn=False,
                  rep_head=False):
-        super().__init__()
-        for name, val in (("in_planes", in_planes), ("inner_planes", inner_planes), ("key_planes", key_planes)):
-            if int(val) < 4 or int(val) % 4:
-                raise ValueError("dec_ccnet: %s (%r) must be a positive multiple of 4 (float4 rows)" % (name, val))
+        _check_planes("dec_ccnet", in_planes=in_planes, inner_planes=inner_planes, key_planes=key_planes)
         if int(recurrence) < 1:
             raise ValueError("dec_ccnet: recurrence must be >= 1, got %r" % (recurrence,))
-        if not 2 <= int(num_classes) <= K.REGION_MAX_K:
-            raise ValueError("dec_ccnet: 2 <= num_classes <= %d (what the loss path takes), got %r" % (K.REGION_MAX_K, num_classes))
-        norm_layer = norm_layer_for(sync_bn)
-        self.rep_head, self.recurrence, self.shared = rep_head, int(recurrence), bool(shared)
+        _check_num_classes("dec_ccnet", num_classes)
+        super().__init__(in_planes, num_classes, inner_planes, sync_bn, rep_head, key_planes=key_planes, recurrence=int(recurrence),
+                         shared=bool(shared))
 
-        def unit3x3(cin, cout, *tail):
-            return nn.Sequential(K.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, dilation=1, bias=False), norm_layer(cout),
-                                 nn.ReLU(inplace=True), *tail)
-
-        self.conva = unit3x3(in_planes, inner_planes)
-        if self.shared:
+    def make_context(self, inner_planes, norm_layer, key_planes, recurrence, shared):
+        self.recurrence, self.shared = recurrence, shared
+        if shared:
             self.cca = CrissCrossBlock(inner_planes, key_planes)
         else:
-            self.cca = nn.ModuleList(CrissCrossBlock(inner_planes, key_planes) for _ in range(self.recurrence))
-        self.convb = unit3x3(inner_planes, inner_planes)
-        self.bottleneck = unit3x3(in_planes + inner_planes, inner_planes, nn.Dropout2d(0.1))
-        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
-        if rep_head:
-            self.representation = nn.Sequential(
-                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
-                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
-                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
+            self.cca = nn.ModuleList(CrissCrossBlock(inner_planes, key_planes) for _ in range(recurrence))
+
+    def context(self, f):
+        for i in range(self.recurrence):
+            f = (self.cca if self.shared else self.cca[i])(f)
+        return f
 
     def check_ranks(self):
         """shared weights collect one gradient per round in the same sinks; the bucketed all-reduce counts one arrival per
@@ -251,19 +286,9 @@ class dec_ccnet(nn.Module):
                                       "under U2PL_DIST_SINGLE; `shared: false` or `recurrence: 1` run there" % self.recurrence)
 
     def forward(self, x, need_rep=True):
-        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
-            x = x[-1]
         if torch.is_grad_enabled():
             self.check_ranks()
-        f = K.run_seq(self.conva, x)
-        for i in range(self.recurrence):
-            f = (self.cca if self.shared else self.cca[i])(f)
-        f = K.run_seq(self.convb, f)
-        out = K.run_seq(self.bottleneck, K.cat_channels((x, f)))
-        res = {"pred": self.classifier(out)}
-        if self.rep_head and need_rep:
-            res["rep"] = K.run_seq(self.representation, out)
-        return res
+        return super().forward(x, need_rep)
 
 
 class NonLocalBlock(nn.Module):
@@ -288,58 +313,33 @@ class NonLocalBlock(nn.Module):
         return K.conv_bn(self.project[0], self.project[1], y, res=x)
 
 
-class dec_nonlocal(nn.Module):
+class dec_nonlocal(_ContextHead):
     """Non-local head (Wang et al., CVPR 2018; the position attention of DANet, Fu et al., CVPR 2019, is this block with
-    value_planes = inner_planes; no reference line: the reference has the two ASPP heads only), shaped as dec_ccnet with a
-    NonLocalBlock in the place of the criss-cross rounds.  conva: 3x3 to inner_planes -> norm -> ReLU; nl: every pixel attends
-    to every pixel (K.dense_attention, csrc/attn.hip: tiled, online softmax, nothing of size pixels x pixels stored, so no cap on
-    the map); convb: 3x3 -> norm -> ReLU; bottleneck: 3x3 over cat(input, convb) -> norm -> ReLU -> Dropout2d(0.1); classifier:
-    1x1 with bias.  rep_head: dec_pspnet's `representation` tower on the bottleneck.  key_planes / heads <= K.ATTN_MAX_D and
-    value_planes / heads <= K.ATTN_MAX_DV per head.  Out of scope, refused or absent: masks and causal attention, dropout on
+    value_planes = inner_planes; no reference line: the reference has the two ASPP heads only): a _ContextHead whose block is
+    nl: a NonLocalBlock in the place of dec_ccnet's criss-cross rounds, every pixel attends to every pixel (K.dense_attention,
+    csrc/attn.hip: tiled, online softmax, nothing of size pixels x pixels stored, so no cap on the map).  key_planes / heads <=
+    K.ATTN_MAX_D and value_planes / heads <= K.ATTN_MAX_DV per head.  Out of scope, refused or absent: masks and causal attention, dropout on
     the weights, relative position terms, a fused q/k/v projection, DANet's channel-attention branch, the fp16 prediction path."""
 
     def __init__(self, in_planes, num_classes=19, inner_planes=512, key_planes=64, value_planes=256, heads=1, kv_stride=1,
                  scale=None, sync_bn=False, rep_head=False):
-        super().__init__()
-        for name, val in (("in_planes", in_planes), ("inner_planes", inner_planes), ("key_planes", key_planes),
-                          ("value_planes", value_planes)):
-            if int(val) < 4 or int(val) % 4:
-                raise ValueError("dec_nonlocal: %s (%r) must be a positive multiple of 4 (float4 rows)" % (name, val))
+        _check_planes("dec_nonlocal", in_planes=in_planes, inner_planes=inner_planes, key_planes=key_planes,
+                      value_planes=value_planes)
         if int(heads) < 1 or int(key_planes) % int(heads) or int(value_planes) % int(heads):
             raise ValueError("dec_nonlocal: key_planes (%r) and value_planes (%r) must divide into heads (%r)" % (
                 key_planes, value_planes, heads))
         K.check_attn_shapes(1, heads, 1, 1, int(key_planes) // int(heads), int(value_planes) // int(heads), "dec_nonlocal")
         if kv_stride not in (1, 2):
             raise ValueError("dec_nonlocal: kv_stride must be 1 or 2, got %r" % (kv_stride,))
-        if not 2 <= int(num_classes) <= K.REGION_MAX_K:
-            raise ValueError("dec_nonlocal: 2 <= num_classes <= %d (what the loss path takes), got %r" % (K.REGION_MAX_K, num_classes))
-        norm_layer = norm_layer_for(sync_bn)
-        self.rep_head = rep_head
+        _check_num_classes("dec_nonlocal", num_classes)
+        super().__init__(in_planes, num_classes, inner_planes, sync_bn, rep_head, key_planes=key_planes, value_planes=value_planes,
+                         heads=heads, kv_stride=kv_stride, scale=scale)
 
-        def unit3x3(cin, cout, *tail):
-            return nn.Sequential(K.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, dilation=1, bias=False), norm_layer(cout),
-                                 nn.ReLU(inplace=True), *tail)
+    def make_context(self, inner_planes, norm_layer, **block):
+        self.nl = NonLocalBlock(inner_planes, norm_layer=norm_layer, **block)
 
-        self.conva = unit3x3(in_planes, inner_planes)
-        self.nl = NonLocalBlock(inner_planes, key_planes, value_planes, heads, kv_stride, scale, norm_layer)
-        self.convb = unit3x3(inner_planes, inner_planes)
-        self.bottleneck = unit3x3(in_planes + inner_planes, inner_planes, nn.Dropout2d(0.1))
-        self.classifier = K.Conv2d(inner_planes, num_classes, kernel_size=1, stride=1, padding=0, bias=True)
-        if rep_head:
-            self.representation = nn.Sequential(
-                K.Conv2d(inner_planes, 256, kernel_size=3, stride=1, padding=1, bias=False),
-                norm_layer(256), nn.ReLU(inplace=True), nn.Dropout2d(0.1),
-                K.Conv2d(256, 256, kernel_size=1, stride=1, padding=0, bias=True))
-
-    def forward(self, x, need_rep=True):
-        if isinstance(x, (list, tuple)):      # the encoder's four maps (fpn: true): the head reads the last
-            x = x[-1]
-        f = K.run_seq(self.convb, self.nl(K.run_seq(self.conva, x)))
-        out = K.run_seq(self.bottleneck, K.cat_channels((x, f)))
-        res = {"pred": self.classifier(out)}
-        if self.rep_head and need_rep:
-            res["rep"] = K.run_seq(self.representation, out)
-        return res
+    def context(self, f):
+        return self.nl(f)
 
 
 class Aux_Module(nn.Module):
